@@ -10,9 +10,16 @@ timed region), obs int32 (the reference dtype).  One "step" = one fused
 Multi-GPU (torchrun, one process per GPU): independent env shards, no
 collective on the data path; barrier + synchronize around the timed region,
 max elapsed over ranks; value = all ranks' env-steps / that time (weak scaling).
-``python bench.py --gpus N`` without torchrun's env times the CPU baselines and
-then starts ``python -m torch.distributed.run --nproc-per-node N bench.py ...``
+``python bench.py --gpus N`` without torchrun's env times the CPU baselines (``--full``)
+and then starts ``python -m torch.distributed.run --nproc-per-node N bench.py ...``
 as a child process; a world size that disagrees with ``--gpus`` fails.
+
+A plain run (``--gpus 1 --steps K --warmup W``) does only what the headline figure needs: it
+sets up the env shard, pre-rolls and warms up, times the K steps and prints the line, whose
+side-leg fields are then null or empty.  ``--dump-outputs DIR`` also writes what the last
+timed step computed as ``DIR/<name>.npy``; the same arguments give the same inputs, and so the
+same arrays, in every run.  Everything below -- the CPU baselines, the env side legs, the
+clock-stamped launches and the MAPPO legs -- runs with ``--full`` only.
 
 MAPPO legs (the metric's "MAPPO updates/sec"): one full train cycle of the device
 learner -- rollout of T steps (actor + critic forward, sampling, fused env step with
@@ -642,12 +649,42 @@ def stamp_phases(log) -> Optional[dict]:
             "phase_median_us": {n: med(v) for n, v in ph.items()}, "launches": len(span)}
 
 
+DUMP_OBS_BYTES = 48 << 20  # --dump-outputs: float32 bytes of observation rows kept (whole dump < 64 MB)
+
+
+def dump_outputs(dump_dir, rank, names, classes, states, obs, outs) -> None:
+    """--dump-outputs: what the last timed env step handed its caller, as float32 ``<name>.npy`` files (every
+    value is a small integer or an fp32 reward, so float32 holds it exactly): the step record (reward, done,
+    solved, num_unsatisfied, episode_step), the state the step left (assignment, episode step, pool row) and the
+    observation rows of a fixed, seeded sample of envs (``obs_envs`` lists them; the whole tensor is ~0.5 GB at
+    the default size).  A mixed run suffixes each name with its size class; ranks > 0 add ``.rank<r>``."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dump_dir, exist_ok=True)
+    budget = DUMP_OBS_BYTES // len(classes)
+    for name, e, st, o, out in zip(names, classes, states, obs, outs):
+        B = st.num_envs
+        n = max(1, min(B, budget // (4 * e.num_agents * e.obs_dim)))
+        rows = np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+        arrays = {k: out[k] for k in ("reward", "done", "solved", "num_unsatisfied", "episode_step")}
+        arrays.update({"state_variable_assignments": st.variable_assignments, "state_step": st.step,
+                       "state_problem_idx": st.problem_idx, "obs": o[torch.from_numpy(rows).to(o.device)],
+                       "obs_envs": rows})
+        for k, v in arrays.items():
+            a = v if isinstance(v, np.ndarray) else v.cpu().numpy()
+            tag = (f"_{name}" if len(classes) > 1 else "") + (f".rank{rank}" if rank else "")
+            np.save(os.path.join(dump_dir, f"{k}{tag}.npy"), a.astype(np.float32))
+
+
 def env_leg(args, rank, world, dist, workload: Optional[str] = None, envs: Optional[int] = None,
-            preroll_s: Optional[float] = None):
+            preroll_s: Optional[float] = None, dump_dir: Optional[str] = None):
     """Time K fused env steps (+ auto-reset) over the local shard; returns the measurement dict.
     workload / envs override --workload / --envs (the side legs).  Before the W warm-up steps, preroll_s
-    seconds of untimed back-to-back launches; after the timed region, --clock-launches launches with the
-    kernel's clock stamps on (msat_step_out.clock_stamps), and one stamped launch first of all (cold)."""
+    seconds of untimed back-to-back launches, after which the envs are put back into their seeded start state
+    (the warm-up and timed steps see the same inputs in every run, however many launches the pre-roll fitted);
+    after the timed region, --clock-launches launches with the kernel's clock stamps on
+    (msat_step_out.clock_stamps), and one stamped launch first of all (cold).  dump_dir: dump_outputs()."""
     import torch
 
     from marlsat import SATEnv
@@ -693,6 +730,9 @@ def env_leg(args, rank, world, dist, workload: Optional[str] = None, envs: Optio
         e0 = classes[0]
         lanes = int(os.environ.get("MARLSAT_ENV_THREADS", "0")) or env_lanes(e0.num_agents, 2 * e0.num_vars + e0.num_clauses, sizes[0])
         kernel = f"env_kernel<2,{'int' if obs_dtype == torch.int32 else 'signed char'},{lanes}>"
+    state_fields = ("variable_assignments", "clauses_satisfied_status", "clause_ntrue", "num_unsatisfied", "step",
+                    "env_done", "problem_idx")
+    start = [[getattr(st, f).clone() for f in state_fields] for st in states]  # the seeded start state
     counter = 1
     # the same launches with the kernel's clock stamps on (a second out record carrying the stamp buffers)
     nclk = args.clock_launches
@@ -734,6 +774,13 @@ def env_leg(args, rank, world, dist, workload: Optional[str] = None, envs: Optio
             n_pre += 1
         torch.cuda.synchronize()
     preroll = {"s": round(time.perf_counter() - t_pre, 3), "launches": n_pre}
+    # the pre-roll fits a different number of launches from run to run: back to the seeded start state and a
+    # fixed RNG counter, so that the warm-up and timed steps compute the same thing in every run
+    for st, saved in zip(states, start):
+        for f, t in zip(state_fields, saved):
+            getattr(st, f).copy_(t)
+        st.reset_serial = 0
+    counter = 1 << 32
     # steady state: after the pre-roll the episode-step counters are set uniform over [0, MAX_STEPS), so
     # ~B/512 envs time out (and auto-reset: new pool instance + assignment drawn in-kernel) in every launch,
     # as in a long-running rollout (solved envs reset on top of that)
@@ -790,6 +837,8 @@ def env_leg(args, rank, world, dist, workload: Optional[str] = None, envs: Optio
     # restarted, so it ends below K; the others advanced by exactly K
     resets = int(sum(int((st.step < K).sum()) for st in states))
     assert all(bool(((st.step < K) | (st.step == sb + K)).all()) for st, sb in zip(states, step_before))
+    if dump_dir:  # before any further launch overwrites the last timed step's buffers
+        dump_outputs(dump_dir, rank, names, classes, states, obs, outs)
     # the clock the kernel ran at, right after the timed region (stamped launches; not timed)
     stamp_log.clear()  # keep the hot launches only
     clk_hot = clock_summary(stamped(nclk, counter)) if nclk else None
@@ -911,7 +960,7 @@ def resolve_world(gpus: Optional[int], environ) -> "int | str | None":
     return "launch" if n > 1 else n
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks, one per GPU (default: torchrun's WORLD_SIZE, else 1); N > 1 without torchrun's env "
@@ -935,10 +984,12 @@ def main():
     ap.add_argument("--mappo-fp32-cycles", type=int, default=1,
                     help="cycles of the headline MAPPO leg rerun on the fp32 path (MARLSAT_PRECISION=fp32, the reference's "
                          "operation order) after its timed cycles: 'fp32_s' beside the default (0: skip)")
-    ap.add_argument("--preroll-s", type=float, default=1.0,
+    ap.add_argument("--preroll-s", type=float, default=10.0,
                     help="seconds of untimed back-to-back env launches before the --warmup steps of the headline env "
                          "leg (the side legs run 0.25 s), so the timed region starts at the clock a long rollout "
-                         "runs at; reported in the line")
+                         "runs at; reported in the line.  10 s: the launch rate still rises by several per cent over "
+                         "the first tens of seconds of load, and after 1 s a run's figure depended on how busy the "
+                         "GPU had been just before it")
     ap.add_argument("--clock-launches", type=int, default=8,
                     help="env launches with the kernel's clock stamps on, right after the timed region (0: none): "
                          "sclk_mhz in the line")
@@ -949,8 +1000,21 @@ def main():
     ap.add_argument("--env-legs", default="uf50-218:1024,uf100-430:4096,mixed:1024,mixed:8192",
                     help="env side legs 'workload:envs_per_gpu,...' ('' skips): BASELINE configs 2 and 3 and config 5 "
                          "(1024 envs per GPU = its 8-GPU share of 8192, and all 8192 on one GPU)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline env leg: the CPU baselines, the env side legs, the MAPPO legs (with "
+                         "their per-kernel and roofline tables and the fp32-path cycles) and the clock-stamped "
+                         "launches; without it --cpu-budget, --env-legs, --mappo* and --clock-launches have no effect")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; "
+                         "dump_outputs() lists the arrays); the same arguments give the same inputs in every run")
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.cpu_budget, args.env_legs, args.mappo, args.clock_launches = 0.0, "", "", 0
+    return args
 
+
+def main():
+    args = parse_args()
     world = resolve_world(args.gpus, os.environ)
     if world == "launch":
         sys.exit(launch_ranks(args))
@@ -993,7 +1057,7 @@ def main():
             raise SystemExit(f"bench.py: --gpus {args.gpus} but the process group has {dist.get_world_size()} ranks")
 
     progress(rank, f"env legs, {world} rank(s)")
-    r = env_leg(args, rank, world, dist)
+    r = env_leg(args, rank, world, dist, dump_dir=args.dump_outputs)
     side_env = env_side_legs(args, rank, world, dist)
     legs = []
     for i, spec in enumerate(filter(None, args.mappo.split(","))):

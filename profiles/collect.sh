@@ -9,8 +9,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof
 TAG=${1:-r01}
 shift || true
-ARGS=${@:-"--steps 200 --warmup 20 --cpu-budget 0 --mappo="}  # the default bench's env leg
-FULL=${MARLSAT_TRACE_ARGS:-"--steps 20 --warmup 5"}  # the driver's bench command (env + MAPPO legs)
+ARGS=${@:-"--full --steps 200 --warmup 20 --cpu-budget 0 --mappo="}  # the full bench's env legs
+FULL=${MARLSAT_TRACE_ARGS:-"--full --steps 20 --warmup 5"}  # the full bench command (env + MAPPO legs)
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $R/bench.py $FULL > $OUT/trace_bench.log 2>&1

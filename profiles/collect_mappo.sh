@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/profm
 mkdir -p $OUT $R/gpurun_out/keep
 trap 'rm -rf $OUT' EXIT  # the raw trace is far larger than what gpurun copies back
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o m -- python3 $R/bench.py --steps 20 --warmup 5 --cpu-budget 0 --mappo $LEG > $OUT/bench.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o m -- python3 $R/bench.py --full --steps 20 --warmup 5 --cpu-budget 0 --mappo $LEG > $OUT/bench.log 2>&1
 W=${LEG%%:*}
 python3 $R/profiles/mappo_slice.py $OUT/m_kernel_trace.csv $OUT/bench.log $R/gpurun_out/keep/${TAG}_mappo_${W}_slice.json
 python3 $R/profiles/gaps.py $OUT/m_kernel_trace.csv ${GAP_WINDOW_S:-36} ${GAP_MIN_US:-3} > $R/gpurun_out/keep/${TAG}_mappo_${W}_gaps.txt || true

@@ -82,6 +82,58 @@ def test_world_from_torchrun_without_gpus_flag():
     assert bench.resolve_world(4, {}) == "launch"
 
 
+def test_plain_run_drops_the_side_work():
+    """Without --full only the headline env leg runs: no CPU baseline, side leg, MAPPO leg or stamped launch,
+    whatever their options say; --full keeps the options' values."""
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3", "--mappo", "uf100-430:4096:8"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    assert (a.cpu_budget, a.env_legs, a.mappo, a.clock_launches) == (0.0, "", "", 0)
+    f = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert f.full and f.dump_outputs == "d"
+    assert f.cpu_budget == 12.0 and f.clock_launches == 8 and f.mappo_fp32_cycles == 1
+    assert f.env_legs.count(",") == 3 and f.mappo == "uf100-430:4096:8,uf200-860:4096:2"
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: float32 .npy files, the step record and state whole, the observation rows of a seeded
+    sample of envs (the same rows in every run) within the byte budget."""
+    from types import SimpleNamespace as NS
+
+    import numpy as np
+    import torch
+
+    import bench
+
+    B, A, V, D = 40, 3, 6, 20
+    g = torch.Generator().manual_seed(0)
+    ri = lambda hi, shape, dt: torch.randint(0, hi, shape, generator=g).to(dt)
+    env = NS(num_agents=A, obs_dim=D)
+    st = NS(num_envs=B, variable_assignments=ri(2, (B, V), torch.uint8), step=ri(512, (B,), torch.int32),
+            problem_idx=ri(1024, (B,), torch.int32))
+    obs = ri(3, (B, A, D), torch.int32) - 1
+    out = {"reward": torch.rand((B,), generator=g), "done": ri(2, (B,), torch.uint8), "solved": ri(2, (B,), torch.uint8),
+           "num_unsatisfied": ri(99, (B,), torch.int32), "episode_step": ri(512, (B,), torch.int32)}
+    for budget, rows in ((bench.DUMP_OBS_BYTES, B), (4 * A * D * 16, 16)):
+        d = tmp_path / str(rows)
+        old, bench.DUMP_OBS_BYTES = bench.DUMP_OBS_BYTES, budget
+        try:
+            bench.dump_outputs(str(d), 0, ("uf20-91",), [env], [st], [obs], [out])
+        finally:
+            bench.DUMP_OBS_BYTES = old
+        got = {p.name[:-4]: np.load(p) for p in d.iterdir()}
+        assert set(got) == set(out) | {"state_variable_assignments", "state_step", "state_problem_idx", "obs", "obs_envs"}
+        assert all(v.dtype == np.float32 for v in got.values())
+        for k, v in out.items():
+            assert np.array_equal(got[k], v.numpy().astype(np.float32))
+        assert np.array_equal(got["state_variable_assignments"], st.variable_assignments.numpy())
+        idx = got["obs_envs"].astype(np.int64)
+        assert idx.shape == (rows,) and np.all(np.diff(idx) > 0) and idx[-1] < B
+        assert np.array_equal(idx, np.sort(np.random.default_rng(0).choice(B, rows, replace=False)))
+        assert np.array_equal(got["obs"], obs.numpy()[idx])
+
+
 def test_side_legs_fit_the_driver_tail():
     """The env side legs and two compact MAPPO legs at 8 ranks close the line within the driver's
     2,000-character tail, which also carries the run's stderr (progress lines, ~350 characters)."""

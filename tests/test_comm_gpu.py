@@ -2,7 +2,7 @@
 world-1 RCCL communicator through the learner's CapiComm handle.  A SUM over one rank is the identity,
 so the buffers must come back bit-identical; the learner's exchange functions run over it unchanged.
 Several ranks need one GPU each (RCCL refuses two ranks per device), so N > 1 over this route is
-`bench.py` under torchrun with MARLSAT_COLLECTIVES=capi on a multi-GPU node (not run by these tests);
+`bench.py --full` under torchrun with MARLSAT_COLLECTIVES=capi on a multi-GPU node (not run by these tests);
 the gloo tests cover the exchange logic with world 2."""
 import ctypes
 
