@@ -189,6 +189,15 @@ int msat_env_step_grouped(int32_t num_groups, const msat_env_desc *descs, const 
                           uint64_t seed, uint64_t rng_counter, const msat_step_out *outs, void *const *obs,
                           void *stream);
 
+/* Workgroup size (lanes per env) that msat_env_reset / msat_env_step / msat_env_obs launch with for desc (chosen
+ * from num_agents * (2 num_vars + num_clauses) and num_envs), and the one msat_env_*_grouped launch with for
+ * total_envs envs over all classes: exactly what the launches use, the MARLSAT_ENV_THREADS /
+ * MARLSAT_ENV_GROUP_THREADS overrides (read once per process) included.  Host-only: no GPU call.  A bad desc or
+ * total_envs < 0: MSAT_EBADARG.  For tests and benchmark labels that name the kernel instantiation that ran.
+ * (Additive entry points: msat_version() stays 3, no struct changed.) */
+int msat_env_launch_threads(const msat_env_desc *desc);
+int msat_env_group_launch_threads(int32_t total_envs);
+
 /* obs may be NULL in msat_env_reset / msat_env_step: state-only update, no observation write
  * (the single-agent SatEnv observes the GNN input instead, src/envs/sat_env.py:120-166). */
 

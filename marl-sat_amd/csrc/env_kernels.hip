@@ -1167,6 +1167,18 @@ static int launch_env(const EnvParams &p, const msat_env_desc *d, const msat_poo
     return check_launch("env_kernel");
 }
 
+// Workgroup size of the grouped launch: 512 lanes for small batches (<= 2048 envs over all classes: the launch is
+// bound by one large env's latency; mixed 1024: 15.7 vs 16.9 us), 256 otherwise (mixed 8192: 91.5-96.9 vs 105.5 us
+// on 512); MARLSAT_ENV_GROUP_THREADS (256 / 512 / 1024) overrides
+static int group_threads(int total) {
+    static const int forced = [] {
+        const char *e = getenv("MARLSAT_ENV_GROUP_THREADS");
+        const int v = e ? atoi(e) : 0;
+        return v == 256 || v == 512 || v == 1024 ? v : 0;
+    }();
+    return forced ? forced : (total <= 2048 ? 512 : 256);
+}
+
 template <int MODE>
 static int launch_groups(int G, const msat_env_desc *descs, const msat_pool *pools, const msat_env_state *states,
                          const int32_t *const *actions, uint64_t seed, uint64_t ctr, const msat_step_out *outs,
@@ -1217,15 +1229,7 @@ static int launch_groups(int G, const msat_env_desc *descs, const msat_pool *poo
     MSAT_REQUIRE(lds <= 160 * 1024, "env needs %zu B of LDS (> 160 KiB)", lds);
     gs.total = total;
     if (total == 0) return MSAT_OK;
-    // workgroup size: 512 lanes for small batches (<= 2048 envs: the launch is bound by one large env's
-    // latency; mixed 1024: 15.7 vs 16.9 us), 256 otherwise (mixed 8192: 91.5-96.9 vs 105.5 us on
-    // 512); MARLSAT_ENV_GROUP_THREADS (256 / 512 / 1024) overrides
-    static const int forced = [] {
-        const char *e = getenv("MARLSAT_ENV_GROUP_THREADS");
-        const int v = e ? atoi(e) : 0;
-        return v == 256 || v == 512 || v == 1024 ? v : 0;
-    }();
-    const int gT = forced ? forced : (total <= 2048 ? 512 : 256);
+    const int gT = group_threads(total);
 #define MSAT_GROUP_LAUNCH(TT)                                                                                      \
     if (descs[0].obs_dtype == MSAT_OBS_I32)                                                                        \
         hipLaunchKernelGGL((env_group_kernel<MODE, int32_t, TT>), dim3(total), dim3(TT), lds, s, gs, seed, ctr);   \
@@ -1262,6 +1266,18 @@ extern "C" int msat_env_step_grouped(int32_t num_groups, const msat_env_desc *de
                                                  obs, (hipStream_t)stream);
     return launch_groups<kModeStep>(num_groups, descs, pools, states, actions, seed, rng_counter, outs, obs,
                                     (hipStream_t)stream);
+}
+
+// The workgroup sizes the launches above use (host-only; tests and labels name the instantiation that ran)
+extern "C" int msat_env_launch_threads(const msat_env_desc *desc) {
+    EnvParams p;
+    if (int rc = make_params(desc, &p)) return rc;
+    return env_threads(p);
+}
+
+extern "C" int msat_env_group_launch_threads(int32_t total_envs) {
+    MSAT_REQUIRE(total_envs >= 0, "total_envs %d < 0", total_envs);
+    return group_threads(total_envs);
 }
 
 extern "C" size_t msat_reset_queue_words(int32_t num_envs) { return num_envs < 0 ? 0 : rq_words(num_envs); }

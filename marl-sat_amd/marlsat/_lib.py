@@ -103,6 +103,8 @@ def _load():
         "msat_bc_greedy_labels": (c_int32, [POINTER(EnvDesc), P, P, P, c_float, P, P, P]),
         "msat_static_var_features": (c_int32, [P, c_int32, c_int32, c_int32, P, P]),
         "msat_reset_queue_words": (c_size_t, [c_int32]),
+        "msat_env_launch_threads": (c_int32, [POINTER(EnvDesc)]),
+        "msat_env_group_launch_threads": (c_int32, [c_int32]),
         "msat_gae_workspace_bytes": (c_size_t, [c_int32, c_int32]),
         "msat_gae": (
             c_int32,
@@ -293,6 +295,8 @@ EXPORTED = (
     "msat_gae_workspace_bytes",
     "msat_gae",
     "msat_reset_queue_words",
+    "msat_env_launch_threads",
+    "msat_env_group_launch_threads",
 )
 
 

@@ -96,6 +96,45 @@ def test_reset_queue_size_and_alignment():
     assert rc == -1 and "16-byte aligned" in _lib.lib.msat_last_error().decode()
 
 
+def _forced(var, allowed):
+    v = os.environ.get(var, "")
+    return int(v) if v.isdigit() and int(v) in allowed else 0
+
+
+def test_env_launch_threads_equals_bench_label():
+    """msat_env_launch_threads (the size launch_env uses) against bench.env_lanes, the bench's kernel label, over a
+    grid of (V, C, A, B) with A * D on both sides of each threshold (4096 | 4097, 16383 | 16384) and B on both
+    sides of 1024; msat_env_group_launch_threads around its 2048-env threshold.  Host-only calls."""
+    import bench
+    from marlsat import _lib
+
+    shapes = [  # V, C, A (A <= V; D = 2V + C)
+        (20, 91, 2), (50, 218, 5), (100, 430, 10), (100, 430, 5), (60, 600, 2), (200, 860, 10), (200, 860, 25),
+        (130, 60, 65), (126, 60, 63), (23, 97, 3), (12, 40, 1), (1, 1, 1),
+        (100, 824, 4),   # A * D = 4096
+        (50, 141, 17),   # 4097
+        (100, 181, 43),  # 16383
+        (100, 5261, 3),  # 16383
+        (100, 824, 16),  # 16384
+    ]
+    assert {A * (2 * V + C) for V, C, A in shapes} >= {4096, 4097, 16383, 16384}
+    forced = _forced("MARLSAT_ENV_THREADS", (64, 128, 256, 512))
+    seen = set()
+    for V, C, A in shapes:
+        for B in (1, 8, 1023, 1024, 1025, 1032, 2048, 4096, 8192):
+            d = _desc(num_envs=B, num_vars=V, num_clauses=C, num_agents=A, max_vars_per_agent=-(-V // A))
+            got = _lib.lib.msat_env_launch_threads(ctypes.byref(d))
+            assert got == (forced or bench.env_lanes(A, 2 * V + C, B)), (V, C, A, B, got)
+            seen.add(got)
+    assert forced or seen == {64, 128, 256, 512}
+    assert _lib.lib.msat_env_launch_threads(ctypes.byref(_desc(num_vars=0))) == -1
+    assert "num_vars" in _lib.lib.msat_last_error().decode()
+    gforced = _forced("MARLSAT_ENV_GROUP_THREADS", (256, 512, 1024))
+    for total, want in ((0, 512), (1, 512), (2048, 512), (2049, 256), (8192, 256)):
+        assert _lib.lib.msat_env_group_launch_threads(total) == (gforced or want), total
+    assert _lib.lib.msat_env_group_launch_threads(-1) == -1
+
+
 def test_gae_bad_dims_rejected():
     from marlsat import _lib
 

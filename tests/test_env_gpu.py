@@ -139,8 +139,11 @@ def test_step_env_functional_api_and_solve():
 @pytest.mark.parametrize("reward_mode", [0, 1])
 @pytest.mark.parametrize("action_mode", [0, 1])
 def test_modes_match_oracle(reward_mode, action_mode):
-    V, C, B, N = 30, 126, 9, 4
-    env, ora = _mk(V, C, 7, max_steps=4, reward_mode=reward_mode, action_mode=action_mode, r_clause=0.03,
+    _modes_rollout(30, 126, 7, 9, 4, reward_mode, action_mode)
+
+
+def _modes_rollout(V, C, vpa, B, N, reward_mode, action_mode):
+    env, ora = _mk(V, C, vpa, max_steps=4, reward_mode=reward_mode, action_mode=action_mode, r_clause=0.03,
                    r_sat=5.0, gamma=0.97)
     pool = _pool(V, C, N, seed0=50)
     rng = np.random.default_rng(3)
@@ -535,6 +538,8 @@ def _state_arrays(st):
     (200, 860, 8, 512, 7, False),  # 512-lane workgroups
     (23, 97, 10, 40, 1, False),  # every step times out, and so does the step after a reset
     (50, 218, 10, 2048, 512, False),  # counters from one reset: the whole batch times out together every 512 steps
+    (20, 91, 10, 4100, 4, False),  # B > 4096: the pending scan keeps no bit mask (68 words per lane), ~1025 per step
+    (20, 91, 10, 8192, 512, False),  # 128 words per lane, the mass timeout
 ])
 def test_reset_queue_is_invisible(V, C, vpa, B, max_steps, explicit):
     """The reset queue (msat_env_state.reset_queue: timed-out envs reset in workgroups of their own, listed by the
@@ -557,7 +562,7 @@ def test_reset_queue_is_invisible(V, C, vpa, B, max_steps, explicit):
             s.step.copy_(c)
         sq.invalidate_reset_queue()
     listed = 0
-    if B == 2048:  # all counters one step short of the limit: the mass timeout at the second launch
+    if max_steps == 512 and B >= 2048:  # all counters one step short of the limit: the mass timeout at launch 2
         for s in (sq, sn):
             s.step.fill_(510)
         sq.invalidate_reset_queue()
