@@ -224,21 +224,39 @@ def actor_logits(P, L, svf, x, cf, A_pos, A_neg, agent_vars, action_mask, action
     return torch.where(action_mask[None, :, :, None], vl, torch.tensor(-math.inf, dtype=vl.dtype))
 
 
+def _live_rows(logits):
+    """logits with every all -inf row (a mode-1 padded variable slot) replaced by zeros, so that its
+    log-softmax is finite and sends no gradient back; other rows pass through unchanged."""
+    live = (logits > -math.inf).any(-1, keepdim=True)
+    return torch.where(live, logits, torch.zeros((), dtype=logits.dtype))
+
+
 def log_softmax(logits):
-    return torch.log_softmax(logits, -1)
+    return torch.log_softmax(_live_rows(logits), -1)
 
 
 def entropy(logits):
-    lp = torch.log_softmax(logits, -1)
-    p = lp.exp()
-    return -torch.where(p > 0, p * lp, torch.zeros_like(p)).sum(-1)
+    """-sum p log p with 0 log 0 = 0.  A -inf logit is taken out of the product (log-prob 0, weight 0)
+    rather than selected away afterwards: torch.where(p > 0, p * lp, 0) has a zero gradient times
+    lp = -inf in its backward, which the softmax backward spreads over the row as NaN.  Here a -inf
+    logit receives gradient 0, the rest of its row stays finite, and a row of -inf only gives 0."""
+    on = logits > -math.inf
+    w = on.to(logits.dtype)
+    lp = torch.where(on, log_softmax(logits), torch.zeros((), dtype=logits.dtype))
+    return -(lp.exp() * w * lp).sum(-1)
 
 
-def ppo_loss(P, L, batch, cfg, agent_vars, action_mask, action_mode=0, ent_coef=None):
-    """learner:597-645 -> (total, (value_loss, loss_actor, entropy))."""
-    svf, x, cf, A_pos, A_neg = batch["svf"], batch["x"], batch["cf"], batch["A_pos"], batch["A_neg"]
-    logits = actor_logits(P, L, svf, x, cf, A_pos, A_neg, agent_vars, action_mask, action_mode)
-    value = critic(P, L, svf, x, cf, A_pos, A_neg)
+def clip(x, lo, hi):
+    """jnp.clip = minimum(maximum(x, lo), hi) with tensor bounds: the values of torch.clamp, and the
+    gradient 0.5 at x == lo or x == hi (0.25 at lo == hi == x) where torch.clamp gives 1."""
+    as_t = lambda b: b if torch.is_tensor(b) else torch.tensor(b, dtype=x.dtype)
+    return torch.minimum(torch.maximum(x, as_t(lo)), as_t(hi))
+
+
+def ppo_terms(logits, value, batch, cfg, action_mask, action_mode=0, ent_coef=None):
+    """learner:597-645 from the network's outputs: logits (B,A,M+1) mode 0 / (B,A,M,2) mode 1 (-inf in
+    masked places), value (B,) -> (total, (value_loss, loss_actor, entropy), surrogate (B,A),
+    entropy per distribution (B,A) / (B,A,M), value terms (B,)); the three means are over these."""
     lp_all = log_softmax(logits)
     lp = torch.gather(lp_all, -1, batch["action"].long()[..., None])[..., 0]
     gae = batch["gae"][:, None]
@@ -251,14 +269,26 @@ def ppo_loss(P, L, batch, cfg, agent_vars, action_mask, action_mode=0, ent_coef=
         zero = torch.zeros((), dtype=lp.dtype)
         ratio = torch.exp(torch.where(valid, lp, zero).sum(-1) - torch.where(valid, batch["log_prob"], zero).sum(-1))
     eps = cfg["CLIP_EPS"]
-    loss_actor = -torch.minimum(ratio * gae, torch.clamp(ratio, 1.0 - eps, 1.0 + eps) * gae).mean()
-    ent = entropy(logits).mean()
+    surr = torch.minimum(ratio * gae, clip(ratio, 1.0 - eps, 1.0 + eps) * gae)
+    loss_actor = -surr.mean()
+    ent_rows = entropy(logits)
+    ent = ent_rows.mean()
     c_ent = cfg["ENT_COEF"] if ent_coef is None else ent_coef
     actor_loss = loss_actor - c_ent * ent
     vold = batch["value"]
-    vclip = vold + (value - vold).clamp(-cfg["VF_CLIP"], cfg["VF_CLIP"])
-    vl = 0.5 * torch.maximum((value - batch["targets"]) ** 2, (vclip - batch["targets"]) ** 2).mean()
-    return actor_loss + cfg["VF_COEF"] * vl, (vl, loss_actor, ent), logits, value
+    vclip = vold + clip(value - vold, -cfg["VF_CLIP"], cfg["VF_CLIP"])
+    vmax = torch.maximum((value - batch["targets"]) ** 2, (vclip - batch["targets"]) ** 2)
+    vl = 0.5 * vmax.mean()
+    return actor_loss + cfg["VF_COEF"] * vl, (vl, loss_actor, ent), -surr, ent_rows, 0.5 * vmax
+
+
+def ppo_loss(P, L, batch, cfg, agent_vars, action_mask, action_mode=0, ent_coef=None):
+    """learner:597-645 -> (total, (value_loss, loss_actor, entropy))."""
+    svf, x, cf, A_pos, A_neg = batch["svf"], batch["x"], batch["cf"], batch["A_pos"], batch["A_neg"]
+    logits = actor_logits(P, L, svf, x, cf, A_pos, A_neg, agent_vars, action_mask, action_mode)
+    value = critic(P, L, svf, x, cf, A_pos, A_neg)
+    total, parts, _, _, _ = ppo_terms(logits, value, batch, cfg, action_mask, action_mode, ent_coef)
+    return total, parts, logits, value
 
 
 def adam_update(params, grads, state, lr, b1=0.9, b2=0.999, eps=1e-8):

@@ -8,7 +8,8 @@ from oracle import mappo as om
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("T,B,A", [(1, 1, 1), (7, 13, 2), (32, 4096, 25), (512, 128, 5), (64, 1000, 1)])
+@pytest.mark.parametrize("T,B,A", [(1, 1, 1), (7, 13, 2), (32, 4096, 25), (512, 128, 5), (64, 1000, 1),
+                                   (1, 257, 2)])  # T = 1: the bootstrap value alone; B = 257: a second block of one env
 def test_gae_matches_oracle(T, B, A):
     from marlsat.learners.ops import gae
 
@@ -27,3 +28,23 @@ def test_gae_matches_oracle(T, B, A):
     if T * B > 1:
         onorm, _, _ = om.normalize(oadv)
         np.testing.assert_allclose(adv.cpu().numpy(), onorm, rtol=1e-5, atol=1e-6)
+
+
+def test_gae_every_step_done():
+    """done at every step: nothing is bootstrapped and nothing carried over, so adv = r - v bit for bit
+    (the last value must not leak in) and the targets are r."""
+    from marlsat.learners.ops import gae
+
+    T, B = 6, 70
+    rng = np.random.default_rng(11)
+    r = rng.standard_normal((T, B, 2)).astype(np.float32)
+    v = rng.standard_normal((T, B)).astype(np.float32)
+    d = np.ones((T, B), bool)
+    lv = (100 * rng.standard_normal(B)).astype(np.float32)
+    cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    adv, tgt = gae(cu(r), cu(v), cu(d), cu(lv), 0.995, 0.95, normalize=False)
+    oadv, otgt = om.gae(r[..., 0], v, d, lv, 0.995, 0.95)
+    np.testing.assert_array_equal(adv.cpu().numpy(), oadv)
+    np.testing.assert_array_equal(tgt.cpu().numpy(), otgt)
+    np.testing.assert_array_equal(adv.cpu().numpy(), r[..., 0] - v)
+    assert np.abs(adv.cpu().numpy()).max() < 20  # no trace of the bootstrap values (~100)

@@ -276,12 +276,15 @@ def test_critic_only_batch_matches_full():
     assert torch.equal(v_full, v_crit)
 
 
-@pytest.mark.parametrize("mode", [0, 1])
-def test_ppo_loss_and_grads_match_oracle(mode):
+@pytest.mark.parametrize("mode,padded", [(0, False), (1, False), (0, True)], ids=["0", "1", "0-padded"])
+def test_ppo_loss_and_grads_match_oracle(mode, padded):
     from marlsat import _lib
 
     V, C, vpa, H, L, S = (20, 91, 10, 64, 2, 6) if mode == 0 else (16, 60, 4, 64, 2, 6)
+    if padded:  # agents of 8, 8 and 7 variables: masked lanes in the loss, a -inf logit column, zeroed my_emb slots
+        V, C = 23, 97
     net, b, P, batch, av, am, A, M = _setup(V, C, vpa, H, L, S, mode, seed=5)
+    assert padded == (not bool(am.all()))
     cfg = {"CLIP_EPS": 0.12, "VF_CLIP": 0.5, "ENT_COEF": 0.005, "VF_COEF": 0.5}
     rng = np.random.default_rng(9)
     with torch.no_grad():

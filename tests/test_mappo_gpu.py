@@ -166,6 +166,8 @@ TRAIN_CYCLE_CASES = [
     # the headline MAPPO leg's network (BASELINE config 3): uf100-430, 10 agents of m = 10, H = 128, L = 16,
     # two Adam steps
     (100, 430, 10, 128, 16, 0, (2, 4, 4, 1)),
+    # the padded agents of the second case (8, 8, 7) in mode 0: a -inf flip logit in the third agent's row
+    (23, 97, 10, 64, 2, 0, (2, 4, 4, 2)),
 ]
 
 

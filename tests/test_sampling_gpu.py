@@ -49,3 +49,36 @@ def test_greedy_argmax_first_tie_and_masks():
     act, lp = _sample(lg, True, 0, 0)
     assert act.tolist() == [1, 1, 3, 0]
     assert torch.allclose(lp, torch.log_softmax(lg.double(), 1).gather(1, act.long()[:, None])[:, 0].float())
+
+
+@pytest.mark.parametrize("greedy", [True, False])
+@pytest.mark.parametrize("R", [1, 2, 3, 5])  # one to four waves of the first block busy, then a second block
+@pytest.mark.parametrize("W", [1, 64, 65, 129])  # one lane, a full wave, a second and a third trip of the j += 64 loops
+def test_row_widths_and_row_counts(W, R, greedy):
+    rng = np.random.default_rng(W * 10 + R)
+    lg = (rng.standard_normal((R, W)) * 2).astype(np.float32)
+    if W > 1:
+        lg[rng.random((R, W)) < 0.3] = float("-inf")
+        lg[np.arange(R), rng.integers(0, W, R)] = 0.25  # a live entry in every row
+    logits = torch.from_numpy(lg).cuda()
+    act, lp = _sample(logits, greedy, 99, 5)
+    a = act.long().cpu()
+    assert int(a.min()) >= 0 and int(a.max()) < W
+    assert bool(torch.isfinite(logits.cpu().gather(1, a[:, None])).all())  # never a masked action
+    ref = torch.log_softmax(torch.from_numpy(lg).double(), 1)
+    assert torch.allclose(lp.cpu().double(), ref.gather(1, a[:, None])[:, 0], rtol=0, atol=2e-6)
+    if greedy:
+        assert a.tolist() == np.argmax(lg, 1).tolist()  # the first maximum
+
+
+@pytest.mark.parametrize("greedy", [True, False])
+@pytest.mark.parametrize("W", [2, 11])
+def test_row_without_a_finite_logit(W, greedy):
+    """A mode-1 padded variable slot (W = 2), and the same at W = 11: some action inside the row, and
+    log-prob exactly 0 (the PPO loss skips the slot; a NaN here would poison the joint ratio)."""
+    lg = torch.randn(3, W, device="cuda")
+    lg[1] = float("-inf")
+    act, lp = _sample(lg, greedy, 5, 1)
+    assert 0 <= int(act[1]) < W
+    assert float(lp[1]) == 0.0 and not bool(torch.signbit(lp[1]))
+    assert bool(torch.isfinite(lp).all()) and int(act.min()) >= 0 and int(act.max()) < W
