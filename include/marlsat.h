@@ -210,6 +210,16 @@ int msat_env_group_launch_threads(int32_t total_envs);
 int msat_bc_greedy_labels(const msat_env_desc *desc, const uint16_t *lits, const int32_t *problem_idx,
                           const uint8_t *assign, float tau, int32_t *labels, int32_t *deltas, void *stream);
 
+/* Behavioural-cloning corrupted experts (src/runners/behavioral_cloning.py:121-130) on the device:
+ * dst (S,V) u8, dst[s] = src[clamp(src_row[s], 0, n_src-1)] (src (n_src,V) u8) with n = min(level, V)
+ * DISTINCT variables flipped.  The variables are Floyd's sample, reproducible on the host: for
+ * i = 0..n-1, j = V-n+i, t = (philox4x32_10((counter lo, counter hi, s, i), seed lo, seed hi).x * (j+1)) >> 32;
+ * flip t unless t is already flipped, then flip j.  level = 0 is a plain copy.
+ * S < 0, V < 1, level < 0, n_src < 1, or a NULL pointer with S > 0: MSAT_EBADARG.
+ * (Additive entry point: msat_version() stays 3, no struct changed.) */
+int msat_bc_corrupt(const uint8_t *src, int32_t n_src, const int32_t *src_row, int32_t S, int32_t V,
+                    int32_t level, uint64_t seed, uint64_t counter, uint8_t *dst, void *stream);
+
 /* Single-agent SatEnv clause features [is_sat, is_unsat, 1] (B,C,3) (src/envs/sat_env.py:143-160). */
 int msat_clause_sat_features(const msat_env_desc *desc, const msat_env_state *state,
                              float *clause_features, void *stream);

@@ -264,6 +264,21 @@ int msat_ppo_loss(const float *logits, int32_t S, int32_t A, int32_t M, int32_t 
                   const float *gae, const float *value, const float *old_value, const float *targets,
                   float clip_eps, float vf_clip, float ent_coef, float vf_coef, int32_t minibatch,
                   float *dlogits, float *dvalue, float *row_terms, double *loss_sums, void *stream);
+/* Behavioural-cloning joint cross-entropy (src/runners/behavioral_cloning.py:243-256), action mode 0:
+ * loss = -mean over (sample, agent) of log_softmax(logits)[label].  logits (S*A, M+1), -inf at padded
+ * variable slots; labels (S,A) int32 in [0, M] (M = no-op); minibatch = the number of samples the mean is
+ * over (as msat_ppo_loss: micro-batch gradients add up to the minibatch's).
+ * A row is valid when 0 <= label <= M and logits[label] is finite.  Valid row: dlogits[j] =
+ * (softmax_j - [j == label]) / (minibatch * A) at finite slots, 0 at -inf slots; row_terms[2r] =
+ * -log p[label]; row_terms[2r+1] = 1 if the argmax (lowest index on ties) is the label, else 0.
+ * Invalid row (the reference's loss is inf / NaN there): dlogits row and both row terms are 0, nothing
+ * outside the row is read.  sums[0..3] += (sum nll, sum correct, valid rows, invalid rows), fp64, fixed
+ * order.  dlogits as logits; row_terms 2*S*A floats.  The row's softmax is evaluated in fp64 (its
+ * residuals cancel in the bias gradients), the outputs are rounded to fp32 once.
+ * S < 0, A < 1, M < 1, minibatch < 1, or a NULL pointer with S > 0: MSAT_EBADARG.
+ * (Additive entry point: msat_version() stays 3, no struct changed.) */
+int msat_bc_loss(const float *logits, int32_t S, int32_t A, int32_t M, const int32_t *labels,
+                 int32_t minibatch, float *dlogits, float *row_terms, double *sums, void *stream);
 int msat_adam(float *params, const float *grads, float *m, float *v, size_t n, float lr, float b1, float b2,
               float eps, int32_t count, float grad_scale, void *stream);
 /* msat_adam + a fail-loud guard: if an updated parameter is not finite, *first_bad = min(*first_bad,

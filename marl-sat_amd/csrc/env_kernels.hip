@@ -1019,6 +1019,33 @@ bc_labels_kernel(EnvParams p, const uint16_t *__restrict__ lits, const int32_t *
     }
 }
 
+// ------------------------------------------------- BC corrupted experts ----
+// behavioral_cloning.py:121-130 for a batch: sample s is expert row src_row[s] (clamped into the table)
+// with n = min(level, V) distinct variables flipped.  The n variables are Floyd's sample of [0, V): for
+// i = 0..n-1, j = V - n + i, t = mulhi32(philox(counter, s, i).x, j + 1) in [0, j]; take t unless it is
+// already taken, then j (never taken before: earlier picks are <= j - 1).  Every pick flips once, so
+// "taken" is dst != src at that position and the sample needs no scratch.  One thread per sample: the
+// draws of a sample are sequential and each thread reads back only bytes it stored itself (a one-off
+// preprocessing pass over N x NUM_SAMPLES_PER_EXPERT rows of V bytes).
+__global__ void __launch_bounds__(256)
+bc_corrupt_kernel(const uint8_t *__restrict__ src, int n_src, const int32_t *__restrict__ src_row, int S, int V,
+                  int n, uint64_t seed, uint64_t ctr, uint8_t *__restrict__ dst) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const uint8_t *x = src + (size_t)min(max(src_row[s], 0), n_src - 1) * V;
+    uint8_t *y = dst + (size_t)s * V;
+    for (int v = 0; v < V; ++v) y[v] = x[v];
+    for (int i = 0; i < n; ++i) {
+        const int j = V - n + i;
+        const uint4 q = philox4x32_10(make_uint4((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)s, (uint32_t)i),
+                                      (uint32_t)seed, (uint32_t)(seed >> 32));
+        const int t = (int)mulhi32(q.x, (uint32_t)j + 1u);
+        const int pick = y[t] != x[t] ? j : t;
+        MSAT_DCHECK(pick, V);
+        y[pick] = x[pick] ^ 1u;
+    }
+}
+
 // single-agent SatEnv clause features [is_sat, is_unsat, 1] (sat_env.py:143-160)
 __global__ void clause_sat_features_kernel(int BC, const uint8_t *__restrict__ sat, float *__restrict__ f) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1391,6 +1418,19 @@ extern "C" int msat_bc_greedy_labels(const msat_env_desc *desc, const uint16_t *
     hipLaunchKernelGGL(bc_labels_kernel, dim3(p.B), dim3(kThreads), lds, (hipStream_t)stream, p, lits, problem_idx,
                        assign, tau, labels, deltas);
     return check_launch("bc_labels_kernel");
+}
+
+extern "C" int msat_bc_corrupt(const uint8_t *src, int32_t n_src, const int32_t *src_row, int32_t S, int32_t V,
+                               int32_t level, uint64_t seed, uint64_t counter, uint8_t *dst, void *stream) {
+    MSAT_REQUIRE(S >= 0, "bc_corrupt: S %d < 0", S);
+    MSAT_REQUIRE(V >= 1, "bc_corrupt: V %d < 1", V);
+    MSAT_REQUIRE(level >= 0, "bc_corrupt: level %d < 0", level);
+    MSAT_REQUIRE(n_src >= 1, "bc_corrupt: n_src %d < 1", n_src);
+    if (S == 0) return MSAT_OK;
+    MSAT_REQUIRE(src && src_row && dst, "bc_corrupt: NULL pointer");
+    hipLaunchKernelGGL(bc_corrupt_kernel, dim3((S + 255) / 256), dim3(256), 0, (hipStream_t)stream, src, n_src,
+                       src_row, S, V, std::min(level, V), seed, counter, dst);
+    return check_launch("bc_corrupt_kernel");
 }
 
 extern "C" int msat_clause_sat_features(const msat_env_desc *desc, const msat_env_state *state,

@@ -459,6 +459,98 @@ loss_sums_kernel(const float *__restrict__ row_terms, int R, int S, double *__re
     }
 }
 
+// ------------------------------------------------ behavioural cloning loss ----
+// Reference: src/runners/behavioral_cloning.py:243-256 -- loss = -mean over (sample, agent) of
+// log_softmax(logits)[label].  A row is valid when its label is inside the row and points at a finite
+// logit; the reference's loss is inf / NaN on any other row, here the row contributes nothing and is
+// counted (the learner raises on the count).
+__device__ __forceinline__ bool bc_row_valid(const float *__restrict__ lg, int W, int label) {
+    const int a = min(max(label, 0), W - 1);  // never index outside the row
+    const float la = lg[a];
+    return a == label && la > -INFINITY && la < INFINITY;
+}
+
+// One wave per (s, agent) row of width W = M+1.  Writes dlogits = (softmax - onehot(label)) * inv_n and
+// the row terms (-log p[label], argmax == label); an invalid row gets zeros throughout.
+__global__ void __launch_bounds__(256)
+bc_loss_kernel(const float *__restrict__ logits, int R, int W, const int32_t *__restrict__ labels, double inv_n,
+               float *__restrict__ dlogits, float *__restrict__ row_terms) {
+    const int lane = threadIdx.x & 63;
+    for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < R; r += gridDim.x * 4) {
+        const float *lg = logits + (size_t)r * W;
+        float *dl = dlogits + (size_t)r * W;
+        const int label = labels[r];
+        const int a = min(max(label, 0), W - 1);
+        if (!bc_row_valid(lg, W, label)) {  // wave-uniform
+            for (int j = lane; j < W; j += 64) dl[j] = 0.f;
+            if (lane == 0) row_terms[2 * (size_t)r] = row_terms[2 * (size_t)r + 1] = 0.f;
+            continue;
+        }
+        // argmax, lowest index on ties (sample_kernel's greedy rule); its value is the row maximum
+        float best = -INFINITY;
+        int bi = 0x7FFFFFFF;
+        for (int j = lane; j < W; j += 64) {
+            const float v = lg[j];
+            if (v > best || (v == best && j < bi)) {
+                best = v;
+                bi = j;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ob = __shfl_xor(best, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (ob > best || (ob == best && oi < bi)) {
+                best = ob;
+                bi = oi;
+            }
+        }
+        // The softmax in fp64, p = e / sum(e) with the same e: the gradient p - onehot is a residual whose row
+        // sum is 0, and the head biases' gradients are sums of these residuals that cancel further as the
+        // actor fits.  row_softmax_stats' fast exp / log and its fp32 logsumexp scale a whole row by ~1 +- 2e-7,
+        // which left the flip-head bias gradient 5e-4 (relative) off the float64 oracle once the residuals had
+        // cancelled to 1e-3 of their terms; here the row sums to 1 to fp64 rounding.  (A few hundred fp64
+        // exps per row, beside a GNN forward / backward per sample.)
+        const double m = (double)best;
+        double sum = 0.0;
+        for (int j = lane; j < W; j += 64) sum += exp((double)lg[j] - m);  // exp(-inf) = 0 at padded slots
+        sum = wave_sum_f64(sum);
+        for (int j = lane; j < W; j += 64) {
+            const double p = exp((double)lg[j] - m) / sum;
+            dl[j] = (float)((p - (j == a ? 1.0 : 0.0)) * inv_n);
+        }
+        if (lane == 0) {
+            row_terms[2 * (size_t)r] = (float)(log(sum) - ((double)lg[a] - m));
+            row_terms[2 * (size_t)r + 1] = bi == a ? 1.0f : 0.0f;
+        }
+    }
+}
+
+// sums[0..3] += (nll sum, correct sum, valid rows, invalid rows) in fp64, fixed order
+__global__ void __launch_bounds__(256)
+bc_sums_kernel(const float *__restrict__ logits, int R, int W, const int32_t *__restrict__ labels,
+               const float *__restrict__ row_terms, double *__restrict__ sums) {
+    __shared__ double red[4][256];
+    double nll = 0, ok = 0, nv = 0, ni = 0;
+    for (int r = threadIdx.x; r < R; r += 256) {
+        nll += row_terms[2 * (size_t)r];
+        ok += row_terms[2 * (size_t)r + 1];
+        const bool valid = bc_row_valid(logits + (size_t)r * W, W, labels[r]);
+        nv += valid ? 1.0 : 0.0;
+        ni += valid ? 0.0 : 1.0;
+    }
+    red[0][threadIdx.x] = nll;
+    red[1][threadIdx.x] = ok;
+    red[2][threadIdx.x] = nv;
+    red[3][threadIdx.x] = ni;
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double t = 0;
+        for (int k = 0; k < 256; ++k) t += red[threadIdx.x][k];
+        sums[threadIdx.x] += t;
+    }
+}
+
 // ------------------------------------------------------------------- Adam ----
 // optax.adam: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr * mhat / (sqrt(vhat) + eps)
 // first_bad (nullable): atomicMin(first_bad, count) where an updated parameter is not finite (a
@@ -622,6 +714,26 @@ extern "C" int msat_ppo_loss(const float *logits, int32_t S, int32_t A, int32_t 
     if (rc) return rc;
     hipLaunchKernelGGL(loss_sums_kernel, dim3(1), dim3(256), 0, s, row_terms, R, S, loss_sums);
     return check_launch("loss_sums_kernel");
+}
+
+extern "C" int msat_bc_loss(const float *logits, int32_t S, int32_t A, int32_t M, const int32_t *labels,
+                            int32_t minibatch, float *dlogits, float *row_terms, double *sums, void *stream) {
+    MSAT_REQUIRE(S >= 0, "bc_loss: S %d < 0", S);
+    MSAT_REQUIRE(A >= 1, "bc_loss: A %d < 1", A);
+    MSAT_REQUIRE(M >= 1, "bc_loss: M %d < 1", M);
+    MSAT_REQUIRE(minibatch >= 1, "bc_loss: minibatch %d < 1", minibatch);
+    if (!S) return MSAT_OK;
+    MSAT_REQUIRE(logits && labels && dlogits && row_terms && sums, "bc_loss: NULL pointer");
+    MSAT_REQUIRE((long long)S * A <= INT_MAX, "bc_loss: S * A = %lld rows exceed int32", (long long)S * A);
+    const int R = S * A;
+    const double inv_n = 1.0 / ((double)minibatch * (double)A);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bc_loss_kernel, dim3(std::min(8192, (R + 3) / 4)), dim3(256), 0, s, logits, R, M + 1, labels,
+                       inv_n, dlogits, row_terms);
+    int rc = check_launch("bc_loss_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(bc_sums_kernel, dim3(1), dim3(256), 0, s, logits, R, M + 1, labels, row_terms, sums);
+    return check_launch("bc_sums_kernel");
 }
 
 extern "C" int msat_adam_checked(float *params, const float *grads, float *m, float *v, size_t n, float lr, float b1,

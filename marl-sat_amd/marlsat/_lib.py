@@ -101,6 +101,7 @@ def _load():
         "msat_clause_features": (c_int32, [POINTER(EnvDesc), POINTER(EnvStateC), P, P]),
         "msat_clause_sat_features": (c_int32, [POINTER(EnvDesc), POINTER(EnvStateC), P, P]),
         "msat_bc_greedy_labels": (c_int32, [POINTER(EnvDesc), P, P, P, c_float, P, P, P]),
+        "msat_bc_corrupt": (c_int32, [P, c_int32, P, c_int32, c_int32, c_int32, c_uint64, c_uint64, P, P]),
         "msat_static_var_features": (c_int32, [P, c_int32, c_int32, c_int32, P, P]),
         "msat_reset_queue_words": (c_size_t, [c_int32]),
         "msat_env_launch_threads": (c_int32, [POINTER(EnvDesc)]),
@@ -168,6 +169,7 @@ def _load():
     sig["msat_split_dlogits"] = (I, [P, I, I, P, P, P])
     sig["msat_sample_actions"] = (I, [P, I, I, I, U, U, P, P, P])
     sig["msat_ppo_loss"] = (I, [P, I, I, I, I, I, I, P, P, P, P, P, P, F, F, F, F, I, P, P, P, P, P])
+    sig["msat_bc_loss"] = (I, [P, I, I, I, P, I, P, P, P, P])
     sig["msat_gemm_f64acc"] = (I, [P, I, I, P, I, I, P, I, I, I, I, I, P])
     sig["msat_adam"] = (I, [P, P, P, P, Z, F, F, F, F, I, F, P])
     sig["msat_adam_checked"] = (I, [P, P, P, P, Z, F, F, F, F, I, F, P, P])
@@ -268,6 +270,7 @@ EXPORTED = (
     "msat_split_dlogits",
     "msat_sample_actions",
     "msat_ppo_loss",
+    "msat_bc_loss",
     "msat_adam",
     "msat_adam_checked",
     "msat_set_precision",
@@ -287,6 +290,7 @@ EXPORTED = (
     "msat_env_reset_grouped",
     "msat_clause_sat_features",
     "msat_bc_greedy_labels",
+    "msat_bc_corrupt",
     "msat_env_step_grouped",
     "msat_env_obs",
     "msat_env_masks",

@@ -1,0 +1,157 @@
+"""Behavioural-cloning pre-training of the actor on the device -- drop-in for ``train_step`` and the
+epoch loop of src/runners/behavioral_cloning.py (:239-282).
+
+The dataset is (instance id, corrupted assignment, joint greedy labels) per sample
+(runners/behavioral_cloning.preprocess); the GNN input is re-derived on the device from
+(instance, assignment), as in the MAPPO learner.  One epoch is one keyed device permutation of the N
+samples cut into minibatches ``perm[i:i+MINIBATCH_SIZE]`` (the last one may be short and is averaged over
+its own size, :272-276); each minibatch is one gradient of the joint cross-entropy
+``-mean(log_softmax(logits)[label])`` over (sample, agent) (msat_bc_loss; micro-batched like MAPPO, exact:
+per-sample terms add) followed by one Adam step at the constant LEARNING_RATE (``optax.adam(LEARNING_RATE)``,
+:225 -- no schedule, ANNEAL_LR is ignored).  Only the encoder, the actor and the agent embedding receive
+gradient: the critic head is not evaluated, so its gradient is exactly 0 and Adam leaves it bitwise unchanged.
+
+Action mode 0 only (the reference's labels are mode-0 indices) and a single process (BC is a small offline
+job; MAPPO's tests cover the gradient all-reduce).
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, Optional
+
+import torch
+
+from .. import _lib
+from ..envs.multi_agent_sat_env import ProblemPool, SATEnv
+from .gnn import GNNActorCritic
+from .graphs import DeviceTemplates, assemble, batch_totals, build_templates
+from .mappo_gnn_sat_learner import NO_BAD_STEP, activation_plan
+
+L_ = _lib.lib
+
+
+class BCLearner:
+    def __init__(self, config: dict, env: SATEnv, network: GNNActorCritic, pool: ProblemPool,
+                 micro_bytes: Optional[float] = None):
+        if env.action_mode != 0:
+            raise ValueError(f"BCLearner: action_mode {env.action_mode} is not supported: the reference's BC labels "
+                             f"(compute_joint_labels_parallel_greedy) are mode-0 indices (a local variable or the "
+                             f"no-op)")
+        self.cfg = dict(config)
+        self.env, self.net, self.pool = env, network, pool
+        self.device = env.device
+        self.MB = int(config["MINIBATCH_SIZE"])
+        if self.MB < 1:
+            raise ValueError(f"MINIBATCH_SIZE={self.MB} must be >= 1")
+        self.lr = float(config.get("LEARNING_RATE", 3e-4))
+        self.A, self.M = env.num_agents, env.max_vars_per_agent
+        self.tpl = DeviceTemplates(build_templates(pool.clauses.cpu().numpy(), env.num_vars, env.num_agents),
+                                   env.num_agents, self.device)
+        self.micro, _ = activation_plan(config, self.tpl.mean_full_rows, network.H, network.L, self.MB, 1,
+                                        micro_bytes)
+        self.svf = pool.static_var_features()
+        self.N = 0
+        self.data: Optional[Dict[str, torch.Tensor]] = None
+        # parity instrumentation, as MAPPOLearner.trace: a list receives, per Adam step, the minibatch rows, the
+        # parameters it started from, the gradient and the learning rate
+        self.trace: Optional[list] = None
+        self.minibatch_losses = None  # the last epoch's per-minibatch mean losses (numpy, set by train_epoch)
+        self.first_bad = torch.full((1,), NO_BAD_STEP, dtype=torch.int32, device=self.device)
+
+    def set_data(self, problem_idx, assignments, labels) -> None:
+        """The dataset, kept on the device: problem_idx (N,) into the pool, assignments (N, V) u8, labels (N, A)
+        int32 in [0, M] (M = no-op)."""
+        dev = self.device
+        pidx = torch.as_tensor(problem_idx, device=dev).to(torch.int32).contiguous()
+        x = torch.as_tensor(assignments, device=dev).to(torch.uint8).contiguous()
+        lab = torch.as_tensor(labels, device=dev).to(torch.int32).contiguous()
+        N = pidx.numel()
+        if pidx.dim() != 1 or x.shape != (N, self.env.num_vars) or lab.shape != (N, self.A):
+            raise ValueError(f"set_data: expected problem_idx (N,), assignments (N, {self.env.num_vars}), labels "
+                             f"(N, {self.A}); got {tuple(pidx.shape)}, {tuple(x.shape)}, {tuple(lab.shape)}")
+        if N and (int(pidx.min()) < 0 or int(pidx.max()) >= self.pool.clauses.shape[0]):
+            raise ValueError("set_data: problem_idx outside the pool")
+        self.N = N
+        self.data = {"pidx": pidx, "x": x, "labels": lab}
+
+    def gather_rows(self, idx: torch.Tensor):
+        """The dataset rows ``idx`` (int32, device) in one launch (msat_gather_rows): (pidx, x, labels)."""
+        S, dev = idx.numel(), self.device
+        srcs = [self.data["pidx"], self.data["x"], self.data["labels"]]
+        outs = [torch.empty((S,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in srcs]
+        n = len(srcs)
+        src = (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs])
+        dst = (ctypes.c_void_p * n)(*[t.data_ptr() for t in outs])
+        rb = (ctypes.c_int32 * n)(*[t[0].numel() * t.element_size() for t in srcs])
+        _lib.check(L_.msat_gather_rows(idx.data_ptr(), S, n, src, dst, rb, _lib.stream_ptr(dev)), "msat_gather_rows")
+        return outs
+
+    def minibatch_grad(self, idx: torch.Tensor, sums: torch.Tensor, mb_size: int) -> None:
+        """net.grads = d(loss)/d(params) of the joint cross-entropy over the dataset rows ``idx``; ``sums`` (4,)
+        fp64 accumulates (nll, correct, valid rows, invalid rows).  The mean divides by ``mb_size`` samples, so
+        micro-batch gradients add up to the minibatch's."""
+        net, dev, A, M = self.net, self.device, self.A, self.M
+        idx = idx.to(torch.int32).contiguous()
+        net.grads.zero_()
+        bounds = list(range(0, idx.numel(), self.micro)) + [idx.numel()]
+        # every micro-batch's row totals from one device -> host read per minibatch (MAPPOLearner.minibatch_grad)
+        sizes = batch_totals(self.tpl, self.data["pidx"].index_select(0, idx.long()), bounds)
+        for m0, m1, tot in zip(bounds[:-1], bounds[1:], sizes):
+            mi = idx[m0:m1].contiguous()
+            S = mi.numel()
+            pidx, x, lab = self.gather_rows(mi)
+            gb = assemble(self.tpl, self.pool.packed, self.svf, pidx, x, False, tot)
+            logits, _, state = net.forward(gb, critic=False, save=True)
+            dlog = torch.empty_like(logits)
+            rows = torch.empty((2 * S * A,), device=dev)
+            _lib.check(L_.msat_bc_loss(logits.data_ptr(), S, A, M, lab.data_ptr(), mb_size, dlog.data_ptr(),
+                                       rows.data_ptr(), sums.data_ptr(), _lib.stream_ptr(dev)), "msat_bc_loss")
+            net.backward(gb, state, dlog, None)
+            del state
+
+    def permutation(self, generator: torch.Generator) -> torch.Tensor:
+        """A pseudo-random permutation of the N samples, keyed from the host generator's stream and drawn on the
+        device (msat_permutation), as MAPPOLearner.permutation."""
+        seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator))
+        perm = torch.empty((self.N,), dtype=torch.int32, device=self.device)
+        _lib.check(L_.msat_permutation(self.N, seed, 0, perm.data_ptr(), _lib.stream_ptr(self.device)),
+                   "msat_permutation")
+        return perm
+
+    def train_epoch(self, generator: torch.Generator) -> Dict[str, float]:
+        """One pass over the dataset (behavioral_cloning.py:269-280): an Adam step per minibatch; returns the mean
+        of the minibatch mean losses and the accuracy (rows whose argmax is the label / valid rows), both from one
+        device -> host read."""
+        if not self.N:
+            raise ValueError("BCLearner.train_epoch: no data (set_data first)")
+        net, N, MB, A = self.net, self.N, self.MB, self.A
+        starts = list(range(0, N, MB))
+        sums = torch.zeros((len(starts), 4), dtype=torch.float64, device=self.device)
+        perm = self.permutation(generator)
+        for k, i in enumerate(starts):
+            idx = perm[i:i + MB]
+            self.minibatch_grad(idx, sums[k], idx.numel())
+            if self.trace is not None:
+                self.trace.append({"idx": idx.cpu(), "params": net.params.clone(), "grads": net.grads.clone(),
+                                   "lr": self.lr})
+            net.adam_step(self.lr, first_bad=self.first_bad)
+        s = sums.cpu()
+        bad_labels = int(s[:, 3].sum())
+        if bad_labels:
+            raise ValueError(f"BC: {bad_labels} label(s) of this epoch point at a masked (padded, -inf logit) or "
+                             f"out-of-range action slot; the reference's loss is inf / NaN there.  Labels must be in "
+                             f"[0, M] = [0, {self.M}] and inside the agent's own variables or the no-op")
+        self.check_finite()
+        sizes = torch.tensor([min(MB, N - i) for i in starts], dtype=torch.float64)
+        self.minibatch_losses = (s[:, 0] / (sizes * A)).numpy()  # each minibatch's mean, in Adam-step order
+        loss = float(self.minibatch_losses.mean())
+        return {"loss": loss, "accuracy": float(s[:, 1].sum() / max(float(s[:, 2].sum()), 1.0))}
+
+    def check_finite(self) -> None:
+        """The Adam guard (msat_adam_checked), as MAPPOLearner.check_finite."""
+        bad = int(self.first_bad.item())
+        if bad != NO_BAD_STEP:
+            self.first_bad.fill_(NO_BAD_STEP)
+            raise FloatingPointError(
+                f"BC: Adam step {bad} left non-finite parameters.  A known cause: a problem with a variable in no "
+                f"clause (tests/test_isolated_variable.py; utils.generate_cnf_dataset.has_isolated_variable)")

@@ -65,6 +65,22 @@ def ent_coef_at(update_idx: int, config: dict) -> float:
     return float(c0 - (c0 - c1) * frac)
 
 
+def activation_plan(config: dict, rows: float, H: int, L: int, minibatch: int, num_envs: int,
+                    micro_bytes: Optional[float] = None):
+    """(micro, chunk): the training micro-batch and the inference chunk (samples) that keep the saved
+    activations inside the budget (``micro_bytes``, else MICROBATCH_BYTES); ``rows`` = a sample's mean graph
+    rows (DeviceTemplates.mean_full_rows).  Shared by the MAPPO and the behavioural-cloning learner."""
+    # saved activations per sample (encode tape, fp32, per message step): var rows Hp, Hn, NV, two
+    # G4 tapes = 12H, clause rows Hc, GIN, G4 = 7H (bounded by 12H), plus ~24H of transients
+    per_sample_train = 4.0 * L * rows * 12 * H + 4.0 * rows * 24 * H
+    per_sample_infer = 4.0 * rows * 24 * H
+    budget = micro_bytes if micro_bytes is not None else float(config.get("MICROBATCH_BYTES", 240e9))
+    cap = max(1, min(minibatch, int(budget // per_sample_train)))
+    micro = -(-minibatch // -(-minibatch // cap))  # equal micro-batches, none above the budget
+    chunk = max(1, min(num_envs, int(budget // per_sample_infer)))
+    return micro, chunk
+
+
 # ------------------------------------------------------------- wrapper ----
 @dataclass
 class GNNInput:
@@ -152,16 +168,8 @@ class MAPPOLearner:
         self.n_minibatches = N // self.MB
         self.tpl = DeviceTemplates(build_templates(pool.clauses.cpu().numpy(), env.num_vars, env.num_agents),
                                    env.num_agents, self.device)
-        H, L = network.H, network.L
-        rows = self.tpl.mean_full_rows
-        # saved activations per sample (encode tape, fp32, per message step): var rows Hp, Hn, NV, two
-        # G4 tapes = 12H, clause rows Hc, GIN, G4 = 7H (bounded by 12H), plus ~24H of transients
-        per_sample_train = 4.0 * L * rows * 12 * H + 4.0 * rows * 24 * H
-        per_sample_infer = 4.0 * rows * 24 * H
-        budget = micro_bytes if micro_bytes is not None else float(config.get("MICROBATCH_BYTES", 240e9))
-        cap = max(1, min(self.MB, int(budget // per_sample_train)))
-        self.micro = -(-self.MB // -(-self.MB // cap))  # equal micro-batches, none above the budget
-        self.chunk = max(1, min(self.B, int(budget // per_sample_infer)))
+        self.micro, self.chunk = activation_plan(config, self.tpl.mean_full_rows, network.H, network.L, self.MB,
+                                                 self.B, micro_bytes)
         self.A, self.M = env.num_agents, env.max_vars_per_agent
         self.mode = env.action_mode
         self.svf = pool.static_var_features()

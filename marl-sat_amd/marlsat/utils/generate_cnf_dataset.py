@@ -52,6 +52,14 @@ def generate_sat_clauses(num_vars: int, num_clauses: int, clause_size: int = 3,
     return np.asarray(_planted_clauses(num_vars, num_clauses, clause_size, rnd), dtype=np.int32)
 
 
+def generate_sat_solution(num_vars: int, seed: int) -> np.ndarray:
+    """The hidden solution ``generate_sat_cnf(num_vars, ..., seed=seed)`` plants, 0/1 (V,): the first V draws
+    of the same stream (step 1 above), so it satisfies every clause of that instance whatever its clause
+    count.  Stands in for the reference's pysat-made ``.sol`` files as the BC expert."""
+    rnd = random.Random(seed)
+    return np.array([int(rnd.choice([True, False])) for _ in range(num_vars)], dtype=np.int32)
+
+
 def has_isolated_variable(clauses: np.ndarray, num_vars: int) -> bool:
     """True when some variable 1..num_vars occurs in no clause of the (C, k) literal array."""
     return bool((np.bincount(np.abs(np.asarray(clauses)).ravel() - 1, minlength=num_vars) == 0).any())
@@ -79,11 +87,20 @@ def generate_problem_pool(num_vars: int, num_clauses: int, num_problems: int, si
 
 
 def generate_cnf_dataset_sat(num_files: int, num_vars: int, num_clauses: int, save_dir: str,
-                             seed: Optional[int] = None) -> None:
-    """Writes uf{V}-{i:03d}.cnf files; per-file seeds drawn from one master RNG (reference :45-57)."""
+                             seed: Optional[int] = None, sol_dir: Optional[str] = None) -> None:
+    """Writes uf{V}-{i:03d}.cnf files; per-file seeds drawn from one master RNG (reference :45-57).
+    sol_dir: also write the planted solution of each file as uf{V}-{i:03d}.sol there (one line, signed DIMACS
+    model, what runners/behavioral_cloning.load_expert_data reads); the .cnf bytes do not depend on it."""
     os.makedirs(save_dir, exist_ok=True)
+    if sol_dir is not None:
+        os.makedirs(sol_dir, exist_ok=True)
     rnd = random.Random(seed) if seed is not None else random
     for i in range(1, num_files + 1):
-        text = generate_sat_cnf(num_vars, num_clauses, clause_size=3, seed=rnd.randrange(1 << 30))
+        file_seed = rnd.randrange(1 << 30)
+        text = generate_sat_cnf(num_vars, num_clauses, clause_size=3, seed=file_seed)
         with open(os.path.join(save_dir, f"uf{num_vars}-{i:03d}.cnf"), "w") as f:
             f.write(text)
+        if sol_dir is not None:
+            sol = generate_sat_solution(num_vars, file_seed)
+            with open(os.path.join(sol_dir, f"uf{num_vars}-{i:03d}.sol"), "w") as f:
+                f.write(" ".join(str(v + 1 if b else -(v + 1)) for v, b in enumerate(sol)) + "\n")
