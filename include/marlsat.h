@@ -174,6 +174,28 @@ int msat_env_step(const msat_env_desc *desc, const msat_pool *pool,
                   const uint8_t *new_assign, uint64_t seed, uint64_t rng_counter,
                   const msat_step_out *out, void *obs, void *stream);
 
+/* msat_env_step for a caller whose obs buffer persists from step to step: it writes only the observation
+ * elements that changed.  obs_shadow (device, msat_obs_shadow_words(desc) uint32 words, 4-byte aligned) is the
+ * library's record of what `obs` holds: per env [problem_idx or -1 | assignment bits | clause-satisfied bits].
+ * Fill it with 0xFFFFFFFF words before the first call, and again whenever anything but this entry point (with
+ * this pool and this desc) wrote into `obs`.  An env whose row names its current instance gets only the aligned
+ * groups of delta_group_bytes (16, 64 or 128) bytes in which the observation changed; every other env, every
+ * reset and a step that flips more than a quarter of the env's variable + clause bits write the whole block.
+ * Every env's row is rewritten.  The state arrays may be written by the caller between calls (the new
+ * observation is computed from them, the difference from the shadow).  State, outputs and observation are those
+ * of msat_env_step.  obs_shadow NULL: msat_env_step.  delta_group_bytes 0: whole blocks, rows kept up to date.
+ * obs_shadow with NULL obs, or another delta_group_bytes: MSAT_EBADARG.
+ * (Additive entry points: msat_version() stays 3, no struct changed.) */
+int msat_env_step_delta(const msat_env_desc *desc, const msat_pool *pool,
+                        const msat_env_state *state, const int32_t *actions,
+                        int32_t autoreset, const int32_t *new_problem_idx,
+                        const uint8_t *new_assign, uint64_t seed, uint64_t rng_counter,
+                        const msat_step_out *out, void *obs, uint32_t *obs_shadow,
+                        int32_t delta_group_bytes, void *stream);
+
+/* uint32 words of the obs shadow of desc's batch (0 for an invalid desc). */
+size_t msat_obs_shadow_words(const msat_env_desc *desc);
+
 /* Ragged batches (BASELINE config 5: mixed uf50/uf100/uf200): up to MSAT_MAX_GROUPS size
  * classes, each a homogeneous batch with its own desc / pool / state / obs / actions / outs,
  * advanced by ONE kernel launch (no padding to the largest instance; the reference cannot

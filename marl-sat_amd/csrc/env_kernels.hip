@@ -50,6 +50,15 @@ struct EnvParams {
     uint32_t rq_serial;
 };
 
+// Obs shadow (msat_env_step_delta), an argument of shadow::env_kernel alone: per env, what the obs buffer holds --
+// [problem_idx or -1 | x bit words | clause-sat bit words] (shadow_row_words).  With it a step stores only the obs
+// groups (g aligned bytes: 16 / 64 / 128; 0: whole blocks) in which the image of the shadow row and the image of the
+// new state differ.  EnvParams, and with it every kernel of a launch without a shadow, is what it was without it.
+struct ObsShadowArg {
+    uint32_t *rows;
+    int g;
+};
+
 enum : int { kModeReset = 0, kModeStep = 1, kModeStepAutoReset = 2, kModeObs = 3 };
 
 // Reset queue (msat_env_state.reset_queue): pend[2][B] uint32 tokens.  The launch with serial s reads parity s & 1 --
@@ -146,14 +155,27 @@ struct EnvLds {
     uint32_t *fm;   // [NW]    obs image: element is not -1   (NW = A*D/32 + 2)
     uint32_t *fx;   // [NW]    obs image: element value bit
     int *red;       // [16]    reduction / broadcast scratch
+    // only in a launch with an obs shadow (carve<true>):
+    uint32_t *fd;    // [NW+1] obs image: element differs from what the obs buffer holds (follows fx); G = 16: bit
+                     //        e + fd_shift, so that every 16-byte chunk lies inside one word
+    uint32_t *sx;    // [WV]   the shadow row's assignment bits
+    uint32_t *ssat;  // [WC]   the shadow row's clause-satisfied bits
 };
 
 __host__ __device__ __forceinline__ int obs_image_words(const EnvParams &p) { return (p.A * p.D) / 32 + 2; }
 
-__host__ __device__ __forceinline__ size_t env_lds_words(const EnvParams &p) {
-    return (size_t)p.WV + p.WC + (size_t)p.A * (p.WC + p.WV) + 2 * (size_t)obs_image_words(p) + 16;
+// uint32 words of an env's obs shadow row: problem_idx, ceil(V/32) assignment words, ceil(C/32) clause words
+__host__ __device__ __forceinline__ int shadow_row_words(const EnvParams &p) {
+    return 1 + ((p.V + 31) >> 5) + ((p.C + 31) >> 5);
 }
 
+// a launch with a shadow (sh) carries the third obs image (fd) and the shadow row's bit words (sx, ssat) as well
+__host__ __device__ __forceinline__ size_t env_lds_words(const EnvParams &p, bool sh = false) {
+    return (size_t)p.WV + p.WC + (size_t)p.A * (p.WC + p.WV) + 2 * (size_t)obs_image_words(p) + 16 +
+           (sh ? (size_t)obs_image_words(p) + 1 + p.WV + p.WC : 0);
+}
+
+template <bool SH = false>
 __device__ __forceinline__ EnvLds carve(uint32_t *smem, const EnvParams &p) {
     EnvLds l;
     l.x = smem;
@@ -162,7 +184,10 @@ __device__ __forceinline__ EnvLds carve(uint32_t *smem, const EnvParams &p) {
     l.nbr = l.rel + (size_t)p.A * p.WC;
     l.fm = l.nbr + (size_t)p.A * p.WV;
     l.fx = l.fm + obs_image_words(p);
-    l.red = reinterpret_cast<int *>(l.fx + obs_image_words(p));
+    l.fd = l.fx + obs_image_words(p);
+    l.sx = l.fd + (SH ? obs_image_words(p) + 1 : 0);
+    l.ssat = l.sx + (SH ? p.WV : 0);
+    l.red = reinterpret_cast<int *>(l.ssat + (SH ? p.WC : 0));
     return l;
 }
 
@@ -267,38 +292,44 @@ __device__ __forceinline__ void or_bits(uint32_t *img, int dst, uint32_t bits) {
     }
 }
 
-template <int T>
-__device__ __forceinline__ void build_obs_images(const EnvParams &p, const EnvLds &l) {
+// delta: also FD, the elements whose value differs from the image of the shadow row (l.sx, l.ssat).  The masks are
+// those of the same instance, so FD = (old ^ new) & FM per source word (mostly zero: or_bits returns at once).
+template <int T, bool SH>
+__device__ __forceinline__ void build_obs_images(const EnvParams &p, const EnvLds &l, bool delta, int fd_shift) {
     const int nwV = (p.V + 31) >> 5, nwC = (p.C + 31) >> 5;
     const int U = 2 * nwV + nwC;  // source words per row
     for (int t = threadIdx.x; t < p.A * U; t += T) {
         const int i = t / U;
         int s = t - i * U;
         int len, off;
-        uint32_t m, x;
+        uint32_t m, x, xo = 0;
         if (s < nwV) {  // own vars
             len = min(32, p.V - 32 * s);
             const int lo = agent_lo(p, i) - 32 * s, hi = lo + agent_size(p, i);
             const int a = max(lo, 0), z = min(hi, 32);
             m = z > a ? (low_mask(z) & ~low_mask(a)) : 0u;
             x = l.x[s];
+            if (SH && delta) xo = l.sx[s];
             off = 32 * s;
         } else if ((s -= nwV) < nwC) {  // clause status
             len = min(32, p.C - 32 * s);
             m = l.rel[i * p.WC + s];
             x = l.sat[s];
+            if (SH && delta) xo = l.ssat[s];
             off = p.V + 32 * s;
         } else {  // neighbour vars
             s -= nwC;
             len = min(32, p.V - 32 * s);
             m = l.nbr[i * p.WV + s];
             x = l.x[s];
+            if (SH && delta) xo = l.sx[s];
             off = p.V + p.C + 32 * s;
         }
         const uint32_t keep = low_mask(len);
         const int dst = i * p.D + off;
         or_bits(l.fm, dst, m & keep);
         or_bits(l.fx, dst, x & m & keep);  // value bits only where the element is live
+        if (SH && delta) or_bits(l.fd, dst + fd_shift, (x ^ xo) & m & keep);
     }
 }
 
@@ -356,6 +387,114 @@ __device__ __forceinline__ void write_obs(const EnvParams &p, const EnvLds &l, O
     }
     for (int e = head + nchunks * VEC + threadIdx.x; e < total; e += T)
         o[e] = (ObsT)elem_val(bits_at(l.fm, e), bits_at(l.fx, e), 0);
+}
+
+// Debug builds: an obs chunk a delta step leaves alone must already hold the new image (a caller who wrote into the
+// obs buffer without SATEnv.invalidate_obs shows up here).
+template <typename ObsT>
+__device__ __forceinline__ void dcheck_obs_kept(const EnvLds &l, const ObsT *o, int e, int n) {
+#ifdef MSAT_DEBUG
+    for (int u = 0; u < n; ++u)
+        MSAT_DCHECK((int)o[e + u] == elem_val(bits_at(l.fm, e + u), bits_at(l.fx, e + u), 0) ? 0 : -1 - (e + u), 1);
+#endif
+}
+
+// The delta form of write_obs: the same chunks, each stored only if its aligned group of G bytes (G = 16 / 64 / 128:
+// a power of two >= the chunk, by absolute address, clipped to the env's block) holds an element whose FD bit is set;
+// the unaligned head and tail elements each on their own bit.
+template <int T, typename ObsT>
+__device__ __forceinline__ void write_obs_delta(const EnvParams &p, const EnvLds &l, ObsT *__restrict__ o, int G) {
+    constexpr int VEC = ObsVec<ObsT>::N;
+    const int total = p.A * p.D;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(o) / sizeof(ObsT);  // o[0]'s absolute element index
+    const int GE = G / (int)sizeof(ObsT);                                 // elements per group
+    int head = (int)(a0 % VEC);
+    head = head ? VEC - head : 0;
+    head = min(head, total);
+    for (int e = threadIdx.x; e < head; e += T) {
+        if (bit(l.fd, e))
+            o[e] = (ObsT)elem_val(bits_at(l.fm, e), bits_at(l.fx, e), 0);
+        else
+            dcheck_obs_kept(l, o, e, 1);
+    }
+    const int nchunks = (total - head) / VEC;
+    for (int q = threadIdx.x; q < nchunks; q += T) {
+        const int e = head + q * VEC;
+        const int gs = e - (int)((a0 + (uintptr_t)e) & (uintptr_t)(GE - 1));  // the group's first element (< 0: clipped)
+        const int lo = max(gs, 0), hi = min(gs + GE, total);
+        uint32_t any = 0;
+        for (int k = lo; k < hi; k += 32) any |= bits_at(l.fd, k) & low_mask(hi - k);
+        if (any)
+            ObsVec<ObsT>::store(o + e, bits_at(l.fm, e), bits_at(l.fx, e));
+        else
+            dcheck_obs_kept(l, o, e, VEC);
+    }
+    for (int e = head + nchunks * VEC + threadIdx.x; e < total; e += T) {
+        if (bit(l.fd, e))
+            o[e] = (ObsT)elem_val(bits_at(l.fm, e), bits_at(l.fx, e), 0);
+        else
+            dcheck_obs_kept(l, o, e, 1);
+    }
+}
+
+__device__ __forceinline__ void lds_barrier();  // below, with the kernel
+
+// One dirty chunk of the G = 16 delta write: shifted element index ec (a multiple of VEC), i.e. elements
+// [ec - sh, ec - sh + VEC) of the block -- the 16-byte store, or element stores where the block starts or ends
+// inside the chunk.
+template <typename ObsT>
+__device__ __forceinline__ void store_chunk16(const EnvParams &p, const EnvLds &l, ObsT *__restrict__ o, int ec, int sh) {
+    constexpr int VEC = ObsVec<ObsT>::N;
+    const int total = p.A * p.D, e = ec - sh;
+    if (e >= 0 && e + VEC <= total) {
+        ObsVec<ObsT>::store(o + e, bits_at(l.fm, e), bits_at(l.fx, e));
+    } else {
+        for (int u = max(e, 0); u < min(e + VEC, total); ++u) o[u] = (ObsT)elem_val(bits_at(l.fm, u), bits_at(l.fx, u), 0);
+    }
+}
+
+// The G = 16 delta write.  FD is shifted by sh = (o's element index) mod VEC, so chunk boundaries are multiples of
+// VEC and no chunk straddles an FD word.  Two passes: every lane takes FD words and lists the dirty chunks of its
+// words (most words are zero) in LDS -- the agent tables' words, dead once the images are built; then the listed
+// chunks are stored one per lane, so the stores (and the bit extraction in front of each) run on dense waves.  A
+// chunk that finds the list full is stored by the lane that found it.
+template <int T, typename ObsT>
+__device__ __forceinline__ void write_obs_delta16(const EnvParams &p, const EnvLds &l, ObsT *__restrict__ o, int sh) {
+    constexpr int VEC = ObsVec<ObsT>::N;
+    const int total = p.A * p.D;
+    const int nw = (total + sh + 31) >> 5;
+    uint32_t *list = l.rel;  // rel, nbr contiguous
+    const int cap = p.A * (p.WC + p.WV);
+    int *count = &l.red[7];  // zero so far
+    for (int j = threadIdx.x; j < nw; j += T) {
+        uint32_t d = l.fd[j];
+        if (d == 0) continue;
+        // one bit per dirty chunk, at the chunk's first bit
+        if (VEC == 4) {
+            d |= d >> 1;
+            d |= d >> 2;
+            d &= 0x11111111u;
+        } else {
+            d = ((d & 0xFFFFu) ? 1u : 0u) | ((d >> 16) ? 0x10000u : 0u);
+        }
+        int slot = atomicAdd(count, __popc(d));
+        while (d) {
+            const int ec = 32 * j + __ffs(d) - 1;
+            d &= d - 1;
+            if (slot < cap)
+                list[slot] = (uint32_t)ec;
+            else
+                store_chunk16<ObsT>(p, l, o, ec, sh);
+            ++slot;
+        }
+    }
+    lds_barrier();
+    const int n = min(*count, cap);
+    for (int i = threadIdx.x; i < n; i += T) store_chunk16<ObsT>(p, l, o, (int)list[i], sh);
+#ifdef MSAT_DEBUG
+    for (int e = threadIdx.x; e < total; e += T)  // elements of clean chunks are read back
+        if ((bits_at(l.fd, (e + sh) & ~(VEC - 1)) & low_mask(VEC)) == 0) dcheck_obs_kept(l, o, e, 1);
+#endif
 }
 
 // ---------------------------------------------------------------- kernel ----
@@ -471,12 +610,26 @@ __device__ __forceinline__ void reset_assignment(const EnvParams &p, const EnvLd
 
 // Stage instance pidx's agent tables in LDS (the first kPf* words from this lane's prefetch registers when pf),
 // build the obs bit images and stream the env's (A, D) block.
-template <typename ObsT, int T>
+// SH: the launch has an obs shadow (shadow::env_kernel; without one the code is the plain full write).
+template <typename ObsT, int T, bool SH>
 __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const EnvLds &l, const msat_pool &pool,
                                                     int pidx, bool pf, const uint32_t (&prel)[kPfRel],
                                                     const uint32_t (&pnbr)[kPfNbr], ObsT *__restrict__ o,
-                                                    const ClockStamp *cs) {
+                                                    const ClockStamp *cs, uint32_t *__restrict__ srow, bool delta,
+                                                    int delta_g) {
+    // srow: the env's obs shadow row (NULL: none), rewritten to describe this write.  delta: l.sx / l.ssat hold the
+    // row as it was, it named this instance, and the block holds its image: store only what differs.
     const int tid = threadIdx.x;
+    const int nwV = (p.V + 31) >> 5, nwC = (p.C + 31) >> 5;
+    if (SH && delta)  // source bits that changed (red[6], zero so far): many -> the plain full write
+        for (int t = tid; t < nwV + nwC; t += T) {
+            const int n = t < nwV ? __popc(l.x[t] ^ l.sx[t]) : __popc(l.sat[t - nwV] ^ l.ssat[t - nwV]);
+            if (n) atomicAdd(&l.red[6], n);
+        }
+    if (SH && srow != nullptr) {
+        if (tid == 0) srow[0] = (uint32_t)pidx;
+        for (int t = tid; t < nwV + nwC; t += T) srow[1 + t] = t < nwV ? l.x[t] : l.sat[t - nwV];
+    }
     {
         const uint32_t *rel_g = pool.rel + (size_t)pidx * p.A * p.WC;
         const uint32_t *nbr_g = pool.nbr + (size_t)pidx * p.A * p.WV;
@@ -493,15 +646,27 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
         }
         for (int t = t0r + tid; t < p.A * p.WC; t += T) l.rel[t] = rel_g[t];
         for (int t = t0n + tid; t < p.A * p.WV; t += T) l.nbr[t] = nbr_g[t];
-        for (int t = tid; t < 2 * obs_image_words(p); t += T) l.fm[t] = 0u;  // fm, fx contiguous
+        for (int t = tid; t < (SH && delta ? 3 * obs_image_words(p) + 1 : 2 * obs_image_words(p)); t += T)
+            l.fm[t] = 0u;  // fm, fx, fd contiguous
     }
     lds_barrier();
     if (cs) cs->mark(3);
+    // a step that flipped more than a quarter of the env's variable + clause bits (mode-1 actions can flip them
+    // all) touches most groups anyway: the full write, without the group tests
+    if (!SH || (delta && 4 * l.red[6] > p.V + p.C)) delta = false;
     if ((p.ablate & 3) == 0) {
-        build_obs_images<T>(p, l);
+        // G = 16: FD at bit e + (o's element index mod the chunk), so that chunk k is bits [k VEC, (k + 1) VEC)
+        const int fd_shift =
+            SH && delta && delta_g == 16 ? (int)((reinterpret_cast<uintptr_t>(o) / sizeof(ObsT)) % ObsVec<ObsT>::N) : 0;
+        build_obs_images<T, SH>(p, l, delta, fd_shift);
         lds_barrier();
         if (cs) cs->mark(4);
-        write_obs<T, ObsT>(p, l, o);
+        if (SH && delta && delta_g == 16)
+            write_obs_delta16<T, ObsT>(p, l, o, fd_shift);
+        else if (SH && delta)
+            write_obs_delta<T, ObsT>(p, l, o, delta_g);
+        else
+            write_obs<T, ObsT>(p, l, o);
     } else {
         constexpr int VEC = ObsVec<ObsT>::N;
         const int n = (p.A * p.D) / VEC;
@@ -510,13 +675,14 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
 }
 
 // One environment (index b of its batch) advanced / reset / observed by one workgroup.
-template <int MODE, typename ObsT, int T>
+template <int MODE, typename ObsT, int T, bool SH = false>
 __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &pool, const msat_env_state &st,
                                         const int32_t *__restrict__ actions, const uint8_t *__restrict__ reset_mask,
                                         const int32_t *__restrict__ new_pidx, const uint8_t *__restrict__ new_assign,
                                         uint64_t seed, uint64_t ctr, const msat_step_out &out, ObsT *__restrict__ obs,
-                                        int b, uint32_t *smem, const ClockStamp &cs) {
-    const EnvLds l = carve(smem, p);
+                                        int b, uint32_t *smem, const ClockStamp &cs,
+                                        const ObsShadowArg sa = ObsShadowArg{nullptr, 0}) {
+    const EnvLds l = carve<SH>(smem, p);
     const int tid = threadIdx.x;
     if (MODE == kModeReset && reset_mask != nullptr && reset_mask[b] == 0) return;
 
@@ -552,6 +718,12 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
         }
         x0 = xg[min(tid, p.V - 1)];
     }
+    // the env's obs shadow row rides in the same round trip: word tid (the few rows longer than the workgroup
+    // load the rest behind the assignment bits)
+    const int srw = shadow_row_words(p);
+    uint32_t *const srow = SH ? sa.rows + (size_t)b * srw : nullptr;
+    uint32_t sh0 = 0;
+    if (SH && MODE != kModeReset) sh0 = srow[min(tid, srw - 1)];  // (SH is a template argument: no branch)
     int pidx = st.problem_idx[b];
     if (MODE != kModeReset) {
         step0 = st.step[b];
@@ -579,6 +751,18 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
         load_x_bits<T>(p, l, xg, x0);
         lds_barrier();
         cs.mark(1);
+        if (SH) {  // the shadow row -> red[5] (the instance it names), l.sx, l.ssat
+            const int nwV = (p.V + 31) >> 5;
+            for (int t = tid; t < srw; t += T) {
+                const uint32_t w = t == tid ? sh0 : srow[t];
+                if (t == 0)
+                    l.red[5] = (int)w;
+                else if (t <= nwV)
+                    l.sx[t - 1] = w;
+                else
+                    l.ssat[t - 1 - nwV] = w;
+            }
+        }
         if (MODE == kModeObs) {
             // get_obs only: no flips, no state update
         } else if (p.action_mode == 0) {
@@ -707,8 +891,11 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
         for (int v = tid; v < p.V; v += T) xg[v] = (uint8_t)bit(l.x, v);
     if ((p.ablate & 3) == 2 || obs == nullptr) return;  // NULL obs: state-only step (single-agent SatEnv)
     // ---- the instance's agent tables (built once per pool instance), obs images, obs stores ----------------
-    stage_and_write_obs<ObsT, T>(p, l, pool, pidx, (MODE != kModeReset) && !do_reset, prel, pnbr,
-                                 obs + (size_t)b * p.A * p.D, &cs);
+    // delta: the block holds the image of its shadow row, and that row names this instance (same masks)
+    const bool delta = SH && (MODE == kModeStep || MODE == kModeStepAutoReset) && sa.g != 0 && !do_reset &&
+                       l.red[5] == pidx;
+    stage_and_write_obs<ObsT, T, SH>(p, l, pool, pidx, (MODE != kModeReset) && !do_reset, prel, pnbr,
+                                     obs + (size_t)b * p.A * p.D, &cs, srow, delta, sa.g);
 }
 
 // A reset workgroup of an autoreset launch with a reset queue (rq_mode 1): the pending env of rank j, i.e. an env that
@@ -716,12 +903,13 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
 // scans the new instance, and writes the clause state, the unsatisfied count and the observation; its step workgroup
 // writes the transition outputs, the assignment, step, done and problem_idx.  Two dependent round trips: the
 // pending words (wave 0's scan), then the pool row and agent tables.
-template <typename ObsT, int T>
+template <typename ObsT, int T, bool SH>
 __device__ __forceinline__ void env_side_reset(const EnvParams &p, const msat_pool &pool, const msat_env_state &st,
                                                const int32_t *__restrict__ new_pidx,
                                                const uint8_t *__restrict__ new_assign, uint64_t seed, uint64_t ctr,
-                                               ObsT *__restrict__ obs, int j, uint32_t *smem) {
-    const EnvLds l = carve(smem, p);
+                                               ObsT *__restrict__ obs, int j, uint32_t *smem,
+                                               const ObsShadowArg sa = ObsShadowArg{nullptr, 0}) {
+    const EnvLds l = carve<SH>(smem, p);
     const int tid = threadIdx.x;
     if (tid < 64) {
         int b = -1;
@@ -745,7 +933,9 @@ __device__ __forceinline__ void env_side_reset(const EnvParams &p, const msat_po
     lds_barrier();
     if (tid == 0) st.num_unsat[b] = l.red[0];
     if ((p.ablate & 3) == 2 || obs == nullptr) return;
-    stage_and_write_obs<ObsT, T>(p, l, pool, pidx, true, prel, pnbr, obs + (size_t)b * p.A * p.D, nullptr);
+    // the whole block and a fresh shadow row (its step workgroup touches neither)
+    stage_and_write_obs<ObsT, T, SH>(p, l, pool, pidx, true, prel, pnbr, obs + (size_t)b * p.A * p.D, nullptr,
+                                     SH ? sa.rows + (size_t)b * shadow_row_words(p) : nullptr, false, 0);
 }
 
 template <int MODE, typename ObsT, int T>
@@ -759,14 +949,45 @@ env_kernel(EnvParams p, msat_pool pool, msat_env_state st, const int32_t *__rest
     // place at the end of the dispatch order made them the launch's tail)
     const int side = (MODE == kModeStepAutoReset && p.rq_mode == 1) ? p.rq_cap : 0;
     if ((int)blockIdx.x < side) {
-        env_side_reset<ObsT, T>(p, pool, st, new_pidx, new_assign, seed, ctr, obs, (int)blockIdx.x, smem);
+        env_side_reset<ObsT, T, false>(p, pool, st, new_pidx, new_assign, seed, ctr, obs, (int)blockIdx.x, smem);
         return;
     }
     const int b = xcd_major((int)blockIdx.x - side, p.B, p.ablate & 4);
     const ClockStamp cs(out.clock_stamps, b);
-    env_run<MODE, ObsT, T>(p, pool, st, actions, reset_mask, new_pidx, new_assign, seed, ctr, out, obs, b, smem, cs);
+    env_run<MODE, ObsT, T, false>(p, pool, st, actions, reset_mask, new_pidx, new_assign, seed, ctr, out, obs, b, smem,
+                                  cs);
     cs.finish();
 }
+
+// The step kernel of a launch with an obs shadow (msat_env_step_delta): the same body with the shadow's loads, LDS
+// words and delta write compiled in (SH), as a kernel of its own under the same name in a nested namespace.  In one
+// body (and then in two bodies under one branch of the one kernel) the shadow code cost the launches WITHOUT a shadow
+// 3-12 % (uf50 x 1,024: 8.45, then 8.03 vs 7.57 us: 65-68 instead of 48 VGPRs, 66-85 instead of 44 spilled SGPRs);
+// apart, they run the code they ran before.  The shadow's pointer and group size are arguments of this kernel alone
+// (ObsShadowArg), not EnvParams fields: 16 more bytes in every env kernel's (and eight times that in the grouped
+// kernel's) arguments and an LDS carve that read them still cost uf50 x 1,024 and mixed x 1,024 1.9 %.
+namespace shadow {
+template <int MODE, typename ObsT, int T>
+__global__ void __launch_bounds__(T)
+env_kernel(EnvParams p, msat_pool pool, msat_env_state st, const int32_t *__restrict__ actions,
+           const uint8_t *__restrict__ reset_mask, const int32_t *__restrict__ new_pidx,
+           const uint8_t *__restrict__ new_assign, uint64_t seed, uint64_t ctr, msat_step_out out,
+           ObsT *__restrict__ obs, uint32_t *__restrict__ shadow_rows, int shadow_g) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const ObsShadowArg sa{shadow_rows, shadow_g};
+    const int side = (MODE == kModeStepAutoReset && p.rq_mode == 1) ? p.rq_cap : 0;
+    if ((int)blockIdx.x < side) {
+        env_side_reset<ObsT, T, true>(p, pool, st, new_pidx, new_assign, seed, ctr, obs, (int)blockIdx.x, smem,
+                                      sa);
+        return;
+    }
+    const int b = xcd_major((int)blockIdx.x - side, p.B, p.ablate & 4);
+    const ClockStamp cs(out.clock_stamps, b);
+    env_run<MODE, ObsT, T, true>(p, pool, st, actions, reset_mask, new_pidx, new_assign, seed, ctr, out, obs, b, smem,
+                                 cs, sa);
+    cs.finish();
+}
+}  // namespace shadow
 
 // Ragged batches (BASELINE config 5): several size classes, each its own (V, C, A) batch with its own
 // pool / state / obs, advanced by ONE launch (256-lane workgroups).  Blocks map to (class, env) with
@@ -787,6 +1008,8 @@ struct EnvGroups {
     int G, total, ablate;
     EnvGroup g[MSAT_MAX_GROUPS];
 };
+
+static_assert(sizeof(EnvGroups) <= 4096, "EnvGroups is passed by value: kernel arguments are limited to 4 KiB");
 
 __host__ __device__ __forceinline__ uint64_t group_seed(int g) { return (uint64_t)g * 0x9E3779B97F4A7C15ull; }
 
@@ -1162,19 +1385,40 @@ template <int MODE>
 static int launch_env(const EnvParams &p, const msat_env_desc *d, const msat_pool *pool,
                       const msat_env_state *st, const int32_t *actions, const uint8_t *mask,
                       const int32_t *npidx, const uint8_t *nassign, uint64_t seed, uint64_t ctr,
-                      const msat_step_out *out, void *obs, hipStream_t s) {
-    const size_t lds = env_lds_words(p) * 4;
+                      const msat_step_out *out, void *obs, hipStream_t s, uint32_t *shadow = nullptr,
+                      int delta_g = 0) {
+    EnvParams pd = p;  // + the buffer extents in debug builds, the reset queue's role
+    // the obs shadow: MARLSAT_ABLATE's obs ablations do not write the observation the rows would describe, so such a
+    // launch leaves them alone -- the rows mean nothing after an ablated launch (diagnostics only)
+    ObsShadowArg sa{nullptr, 0};
+    if ((p.ablate & 3) == 0 && shadow != nullptr) sa = ObsShadowArg{shadow, delta_g};
+    if (MSAT_DEBUG_BUILD && sa.rows != nullptr)
+        MSAT_REQUIRE(dbg_extent(sa.rows, 4) >= (long long)p.B * shadow_row_words(p),
+                     "MSAT_DEBUG: obs_shadow smaller than msat_obs_shadow_words()");
+    const size_t lds = env_lds_words(pd, sa.rows != nullptr) * 4;
     MSAT_REQUIRE(lds <= 160 * 1024, "env needs %zu B of LDS (> 160 KiB)", lds);
     msat_step_out o{};
     if (out) o = *out;
     if (p.B == 0) return MSAT_OK;
     const int T = env_threads(p);
-    EnvParams pd = p;  // + the buffer extents in debug builds, the reset queue's role
     set_dbg_extents(&pd, st, actions, obs, d->obs_dtype);
     if (int rc = set_reset_queue(&pd, st, MODE)) return rc;
     // the reset workgroups of a queue-consuming launch come first (block ids 0 .. cap - 1)
     const int grid = p.B + (pd.rq_mode == 1 ? pd.rq_cap : 0);
 #define MSAT_ENV_LAUNCH(TT)                                                                                        \
+    if constexpr (MODE == kModeStep || MODE == kModeStepAutoReset) {                                               \
+        if (sa.rows != nullptr) {                                                                                  \
+            if (d->obs_dtype == MSAT_OBS_I32)                                                                      \
+                hipLaunchKernelGGL((shadow::env_kernel<MODE, int32_t, TT>), dim3(grid), dim3(TT), lds, s, pd,      \
+                                   *pool, *st, actions, mask, npidx, nassign, seed, ctr, o, (int32_t *)obs, sa.rows, \
+                                   sa.g);                                                                          \
+            else                                                                                                   \
+                hipLaunchKernelGGL((shadow::env_kernel<MODE, int8_t, TT>), dim3(grid), dim3(TT), lds, s, pd,       \
+                                   *pool, *st, actions, mask, npidx, nassign, seed, ctr, o, (int8_t *)obs, sa.rows,  \
+                                   sa.g);                                                                          \
+            return check_launch("env_kernel");                                                                     \
+        }                                                                                                          \
+    }                                                                                                              \
     if (d->obs_dtype == MSAT_OBS_I32)                                                                              \
         hipLaunchKernelGGL((env_kernel<MODE, int32_t, TT>), dim3(grid), dim3(TT), lds, s, pd, *pool, *st, actions, \
                            mask, npidx, nassign, seed, ctr, o, (int32_t *)obs);                                    \
@@ -1363,6 +1607,37 @@ extern "C" int msat_env_step(const msat_env_desc *desc, const msat_pool *pool,
                                               new_assign, seed, rng_counter, out, obs, (hipStream_t)stream);
     return launch_env<kModeStep>(p, desc, pool, state, actions, nullptr, nullptr, nullptr, seed,
                                  rng_counter, out, obs, (hipStream_t)stream);
+}
+
+extern "C" size_t msat_obs_shadow_words(const msat_env_desc *desc) {
+    EnvParams p;
+    if (make_params(desc, &p)) return 0;
+    return (size_t)p.B * shadow_row_words(p);
+}
+
+extern "C" int msat_env_step_delta(const msat_env_desc *desc, const msat_pool *pool, const msat_env_state *state,
+                                   const int32_t *actions, int32_t autoreset, const int32_t *new_problem_idx,
+                                   const uint8_t *new_assign, uint64_t seed, uint64_t rng_counter,
+                                   const msat_step_out *out, void *obs, uint32_t *obs_shadow,
+                                   int32_t delta_group_bytes, void *stream) {
+    EnvParams p;
+    int rc = make_params(desc, &p);
+    if (rc) return rc;
+    MSAT_REQUIRE(delta_group_bytes == 0 || delta_group_bytes == 16 || delta_group_bytes == 64 ||
+                     delta_group_bytes == 128,
+                 "delta_group_bytes %d not 0, 16, 64 or 128", delta_group_bytes);
+    MSAT_REQUIRE(obs_shadow == nullptr || obs != nullptr, "obs_shadow given with NULL obs");
+    MSAT_REQUIRE((reinterpret_cast<uintptr_t>(obs_shadow) & 3) == 0, "obs_shadow must be 4-byte aligned");
+    if (p.B == 0) return MSAT_OK;
+    if ((rc = check_state(state)) || (rc = check_pool(pool))) return rc;
+    MSAT_REQUIRE(actions, "NULL actions");
+    MSAT_REQUIRE(out && out->reward && out->done && out->solved, "NULL step outputs");
+    if (autoreset)
+        return launch_env<kModeStepAutoReset>(p, desc, pool, state, actions, nullptr, new_problem_idx, new_assign,
+                                              seed, rng_counter, out, obs, (hipStream_t)stream, obs_shadow,
+                                              delta_group_bytes);
+    return launch_env<kModeStep>(p, desc, pool, state, actions, nullptr, nullptr, nullptr, seed, rng_counter, out,
+                                 obs, (hipStream_t)stream, obs_shadow, delta_group_bytes);
 }
 
 extern "C" int msat_env_obs(const msat_env_desc *desc, const msat_pool *pool, const msat_env_state *state,

@@ -89,6 +89,12 @@ def _load():
             [POINTER(EnvDesc), POINTER(PoolC), POINTER(EnvStateC), P, c_int32, P, P, c_uint64, c_uint64,
              POINTER(StepOutC), P, P],
         ),
+        "msat_env_step_delta": (
+            c_int32,
+            [POINTER(EnvDesc), POINTER(PoolC), POINTER(EnvStateC), P, c_int32, P, P, c_uint64, c_uint64,
+             POINTER(StepOutC), P, P, c_int32, P],
+        ),
+        "msat_obs_shadow_words": (c_size_t, [POINTER(EnvDesc)]),
         "msat_env_reset_grouped": (
             c_int32, [c_int32, POINTER(EnvDesc), POINTER(PoolC), POINTER(EnvStateC), c_uint64, c_uint64, P, P]
         ),
@@ -287,6 +293,8 @@ EXPORTED = (
     "msat_pool_agent_tables",
     "msat_env_reset",
     "msat_env_step",
+    "msat_env_step_delta",
+    "msat_obs_shadow_words",
     "msat_env_reset_grouped",
     "msat_clause_sat_features",
     "msat_bc_greedy_labels",

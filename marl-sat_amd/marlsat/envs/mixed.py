@@ -20,7 +20,7 @@ import torch
 
 from .. import _lib
 from ..random import as_key
-from .multi_agent_sat_env import ObsDict, ProblemPool, SATEnv, SATState
+from .multi_agent_sat_env import ObsDict, ProblemPool, SATEnv, SATState, _shadow_of
 
 _MASK64 = (1 << 64) - 1
 
@@ -89,6 +89,9 @@ class MixedSATEnv:
         ar = 1 if autoreset else 0
         wants = [(b, c.num_agents) if c.action_mode == 0 else (b, c.num_agents, c.max_vars_per_agent)
                  for c, b in zip(self.classes, sizes)]
+
+        for o in obs:  # the grouped launch writes whole blocks, past what a single-class delta stepper recorded
+            _shadow_of(o).foreign = True
 
         def step(actions: Sequence[torch.Tensor], counter: int) -> None:
             for g in range(G):

@@ -134,6 +134,67 @@ class ProblemPool:
 RESET_QUEUE = os.environ.get("MARLSAT_RESET_QUEUE", "1") != "0"
 
 
+# A step into an obs tensor the library has written before stores only the elements that changed
+# (msat_env_step_delta).  MARLSAT_OBS_DELTA: 1 (default) where that is faster (SATEnv.obs_delta_default), 0 never
+# (every step writes the whole block; A/B runs), 2 for every shape.
+OBS_DELTA = int(os.environ.get("MARLSAT_OBS_DELTA", "1"))
+# int32 blocks of at least this many elements (A * D) take the delta write by default: uf200 (31,500) 80 vs 107 us
+# per launch at 4096 envs; uf100 (6,300) 28.5 vs 26.6, uf50 (1,590) 10.5 vs 8.4 at 1,024 envs and int8 uf200 83 vs 65
+# lose, their launches being bound by each env's chain of dependent steps, not by bytes
+OBS_DELTA_MIN_ELEMS = 16384
+# aligned bytes per stored group, 16 / 64 / 128 (DESIGN.md section 4 has the measurements behind the default)
+OBS_DELTA_GROUP = int(os.environ.get("MARLSAT_OBS_DELTA_GROUP", "16"))
+
+
+class ObsShadow:
+    """What the library last wrote into one obs tensor (msat_env_step_delta's obs_shadow), kept as the tensor
+    object's ``_marlsat_shadow`` attribute: it lives and dies with that object, every stepper bound to the
+    tensor shares it, and a view, a clone or a new tensor at a recycled address has none.  It holds the SATEnv
+    and the ProblemPool it was written under: equal problem_idx under another env or pool may mean other masks."""
+
+    __slots__ = ("words", "env", "pool", "ptr", "foreign")
+
+    def __init__(self):
+        self.words, self.env, self.pool, self.ptr = None, None, None, None
+        # a pre-bound full-write stepper (stepper(obs_delta=False), the grouped stepper) was made for this tensor:
+        # such a stepper does nothing per call for the record (its hot loop is the launch alone), so from then on
+        # no row can be trusted, and for as long as the tensor lives every step into it is the plain full write
+        # (bind() returns None: msat_env_step_delta without a shadow is msat_env_step).  Not cleared by
+        # invalidate_obs(): the full-write stepper may still be in use.
+        self.foreign = False
+
+    def bind(self, env: "SATEnv", pool: "ProblemPool", n: int) -> Optional[int]:
+        """The shadow's device pointer for a step of (env, pool) with n shadow words; rows the buffer may not
+        match (another env / pool / size before, or invalidated) are forgotten first.  None (no shadow: the plain
+        full write) for a tensor that full-write steppers share."""
+        if self.foreign:
+            return None
+        if self.env is not env or self.pool is not pool or self.words.numel() != n:
+            if self.words is None or self.words.numel() != n or self.words.device != env.device:
+                self.words = torch.full((n,), -1, dtype=torch.int32, device=env.device)
+            else:
+                self.words.fill_(-1)
+            self.env, self.pool, self.ptr = env, pool, self.words.data_ptr()
+        return self.ptr
+
+    def invalidate(self) -> None:
+        self.env = self.pool = None  # the rows are wiped by the next bind()
+
+
+def _shadow_of(obs: torch.Tensor) -> ObsShadow:
+    rec = getattr(obs, "_marlsat_shadow", None)
+    if rec is None:
+        rec = obs._marlsat_shadow = ObsShadow()
+    return rec
+
+
+def invalidate_obs(obs) -> None:
+    """Forget what the library knows about obs's contents (no-op for a tensor it never stepped into)."""
+    rec = getattr(obs, "_marlsat_shadow", None) if obs is not None else None
+    if rec is not None:
+        rec.invalidate()
+
+
 @dataclass
 class SATState:
     """``SATState`` (env:13-24) as device SoA tensors with a leading env axis."""
@@ -306,6 +367,23 @@ class SATEnv:
     def alloc_obs(self, num_envs: int) -> torch.Tensor:
         return torch.empty((num_envs, self.num_agents, self.obs_dim), dtype=self.obs_dtype, device=self.device)
 
+    @staticmethod
+    def invalidate_obs(obs: torch.Tensor) -> None:
+        """Call after writing into an obs tensor that ``step_raw`` / ``stepper`` step into: a step stores only
+        the elements that differ from what the library last wrote there, so without this call foreign values
+        survive.  The next step into ``obs`` then writes every block whole.  (The library's own writers --
+        ``reset_from_pool(obs=...)``, the grouped launches -- do this themselves.)"""
+        invalidate_obs(obs)
+
+    def obs_delta_default(self) -> bool:
+        """Whether ``step_raw`` / ``stepper`` take the delta write when ``obs_delta`` is not given."""
+        if OBS_DELTA != 1:
+            return OBS_DELTA != 0
+        return self.obs_dtype == torch.int32 and self.num_agents * self.obs_dim >= OBS_DELTA_MIN_ELEMS
+
+    def _shadow_words(self, num_envs: int, pool: ProblemPool) -> int:
+        return int(_lib.lib.msat_obs_shadow_words(self._desc(num_envs, pool)))
+
     def _actions_tensor(self, actions, B: int) -> torch.Tensor:
         if isinstance(actions, dict):  # learner:131 jnp.stack([actions[a] for a in agents])
             actions = torch.stack([torch.as_tensor(actions[a], device=self.device) for a in self.agents], dim=1)
@@ -355,6 +433,7 @@ class SATEnv:
                                            _lib.ptr(pidx), _lib.ptr(x), k.seed, k.counter, _lib.ptr(obs),
                                            _lib.stream_ptr(self.device)),
                    "msat_env_reset")
+        invalidate_obs(obs)  # (masked or not) written outside the delta step
         state._masks = None
         return obs, state
 
@@ -379,9 +458,12 @@ class SATEnv:
 
     def step_raw(self, state: SATState, actions: torch.Tensor, *, autoreset: bool = False, key=None,
                  problem_idx=None, assignments=None, obs: Optional[torch.Tensor] = None, out=None,
-                 with_obs: bool = True):
+                 with_obs: bool = True, obs_delta: Optional[bool] = None):
         """In-place batched step on device tensors; returns (obs, out-dict). The hot-loop entry point.
-        with_obs=False: no observation write (obs is None)."""
+        with_obs=False: no observation write (obs is None).  obs_delta True: store only the observation elements
+        that differ from what the library last wrote into this ``obs`` tensor object (``invalidate_obs`` after
+        writing into it yourself); False: the whole block; None: ``obs_delta_default()`` (on for large int32
+        blocks unless MARLSAT_OBS_DELTA says otherwise).  The results are the same either way."""
         B = state.num_envs
         a = self._actions_tensor(actions, B)
         if obs is None and with_obs:
@@ -394,19 +476,30 @@ class SATEnv:
         so = _lib.StepOutC(out["reward"].data_ptr(), out["done"].data_ptr(), out["solved"].data_ptr(),
                            out["num_unsatisfied"].data_ptr(), out["episode_step"].data_ptr(),
                            _lib.stamps_ptr(out.get("clock_stamps"), B))
-        _lib.check(_lib.lib.msat_env_step(self._desc(B, state.pool), state.pool.c(self), state._c(),
-                                          a.data_ptr(), 1 if autoreset else 0, _lib.ptr(pidx), _lib.ptr(x), k.seed,
-                                          k.counter, so, _lib.ptr(obs), _lib.stream_ptr(self.device)),
-                   "msat_env_step")
+        if obs is not None and (self.obs_delta_default() if obs_delta is None else obs_delta):
+            shadow = _shadow_of(obs).bind(self, state.pool, self._shadow_words(B, state.pool))
+            _lib.check(_lib.lib.msat_env_step_delta(self._desc(B, state.pool), state.pool.c(self), state._c(),
+                                                    a.data_ptr(), 1 if autoreset else 0, _lib.ptr(pidx), _lib.ptr(x),
+                                                    k.seed, k.counter, so, obs.data_ptr(), shadow, OBS_DELTA_GROUP,
+                                                    _lib.stream_ptr(self.device)),
+                       "msat_env_step_delta")
+        else:
+            _lib.check(_lib.lib.msat_env_step(self._desc(B, state.pool), state.pool.c(self), state._c(),
+                                              a.data_ptr(), 1 if autoreset else 0, _lib.ptr(pidx), _lib.ptr(x),
+                                              k.seed, k.counter, so, _lib.ptr(obs), _lib.stream_ptr(self.device)),
+                       "msat_env_step")
+            invalidate_obs(obs)
         if autoreset:
             state.reset_serial += 1
         state._masks = None
         return obs, out
 
-    def stepper(self, state: SATState, obs: torch.Tensor, out: dict, *, autoreset: bool = True, seed: int = 0):
+    def stepper(self, state: SATState, obs: torch.Tensor, out: dict, *, autoreset: bool = True, seed: int = 0,
+                obs_delta: Optional[bool] = None):
         """Pre-bound in-place step for hot loops: ``f(actions, counter)`` launches one fused
         step (+ auto-reset) on the current stream with no per-call Python marshalling
-        beyond the ctypes call itself.  ``actions`` must be a contiguous device int32 tensor."""
+        beyond the ctypes call itself.  ``actions`` must be a contiguous device int32 tensor.
+        obs_delta: as ``step_raw`` (steppers bound to one obs tensor share its record)."""
         B = state.num_envs
         desc = self._desc(B, state.pool)
         cst = state._c()
@@ -414,7 +507,9 @@ class SATEnv:
         so = _lib.StepOutC(out["reward"].data_ptr(), out["done"].data_ptr(), out["solved"].data_ptr(),
                            out["num_unsatisfied"].data_ptr(), out["episode_step"].data_ptr(),
                            _lib.stamps_ptr(out.get("clock_stamps"), B))
-        fn = _lib.lib.msat_env_step
+        delta = self.obs_delta_default() if obs_delta is None else obs_delta
+        fn = _lib.lib.msat_env_step_delta if delta else _lib.lib.msat_env_step
+        rec, pool, nsh, G = _shadow_of(obs), state.pool, self._shadow_words(B, state.pool), OBS_DELTA_GROUP
         cpool = state.pool.c(self)
         obs_p, s = obs.data_ptr(), _lib.stream_ptr(self.device)
         ar = 1 if autoreset else 0
@@ -432,6 +527,22 @@ class SATEnv:
             if ar:
                 state.reset_serial += 1
 
+        def step_delta(actions: torch.Tensor, counter: int) -> None:
+            if actions.shape != want or actions.dtype != torch.int32:
+                raise ValueError(f"actions must be int32 {want}")
+            cst.reset_serial = state.reset_serial & 0xFFFFFFFF
+            rc = fn(dref, pref, sref, actions.data_ptr(), ar, None, None, seed, counter, oref, obs_p,
+                    rec.bind(self, pool, nsh), G, s)
+            state._masks = None
+            if rc:
+                _lib.check(rc, "msat_env_step_delta")
+            if ar:
+                state.reset_serial += 1
+
+        if delta:
+            step = step_delta
+        else:
+            rec.foreign = True
         step._keepalive = (desc, cpool, cst, so, state, obs, out)
         return step
 
