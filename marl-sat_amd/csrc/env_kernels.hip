@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "obs_sparse.h"
 
 namespace msat {
 
@@ -156,8 +157,8 @@ struct EnvLds {
     uint32_t *fx;   // [NW]    obs image: element value bit
     int *red;       // [16]    reduction / broadcast scratch
     // only in a launch with an obs shadow (carve<true>):
-    uint32_t *fd;    // [NW+1] obs image: element differs from what the obs buffer holds (follows fx); G = 16: bit
-                     //        e + fd_shift, so that every 16-byte chunk lies inside one word
+    uint32_t *fd;    // [NW+1] obs image: element differs from what the obs buffer holds (follows fx; G = 64 / 128).
+                     //        A G = 16 delta step builds no images: fm, fx, fd hold its list of dirty chunks
     uint32_t *sx;    // [WV]   the shadow row's assignment bits
     uint32_t *ssat;  // [WC]   the shadow row's clause-satisfied bits
 };
@@ -292,10 +293,11 @@ __device__ __forceinline__ void or_bits(uint32_t *img, int dst, uint32_t bits) {
     }
 }
 
-// delta: also FD, the elements whose value differs from the image of the shadow row (l.sx, l.ssat).  The masks are
-// those of the same instance, so FD = (old ^ new) & FM per source word (mostly zero: or_bits returns at once).
+// delta (G = 64 / 128; G = 16 builds no images, write_obs_sparse16): also FD, the elements whose value differs from the
+// image of the shadow row (l.sx, l.ssat).  The masks are those of the same instance, so FD = (old ^ new) & FM per
+// source word (mostly zero: or_bits returns at once).
 template <int T, bool SH>
-__device__ __forceinline__ void build_obs_images(const EnvParams &p, const EnvLds &l, bool delta, int fd_shift) {
+__device__ __forceinline__ void build_obs_images(const EnvParams &p, const EnvLds &l, bool delta) {
     const int nwV = (p.V + 31) >> 5, nwC = (p.C + 31) >> 5;
     const int U = 2 * nwV + nwC;  // source words per row
     for (int t = threadIdx.x; t < p.A * U; t += T) {
@@ -329,7 +331,7 @@ __device__ __forceinline__ void build_obs_images(const EnvParams &p, const EnvLd
         const int dst = i * p.D + off;
         or_bits(l.fm, dst, m & keep);
         or_bits(l.fx, dst, x & m & keep);  // value bits only where the element is live
-        if (SH && delta) or_bits(l.fd, dst + fd_shift, (x ^ xo) & m & keep);
+        if (SH && delta) or_bits(l.fd, dst, (x ^ xo) & m & keep);
     }
 }
 
@@ -437,66 +439,6 @@ __device__ __forceinline__ void write_obs_delta(const EnvParams &p, const EnvLds
     }
 }
 
-__device__ __forceinline__ void lds_barrier();  // below, with the kernel
-
-// One dirty chunk of the G = 16 delta write: shifted element index ec (a multiple of VEC), i.e. elements
-// [ec - sh, ec - sh + VEC) of the block -- the 16-byte store, or element stores where the block starts or ends
-// inside the chunk.
-template <typename ObsT>
-__device__ __forceinline__ void store_chunk16(const EnvParams &p, const EnvLds &l, ObsT *__restrict__ o, int ec, int sh) {
-    constexpr int VEC = ObsVec<ObsT>::N;
-    const int total = p.A * p.D, e = ec - sh;
-    if (e >= 0 && e + VEC <= total) {
-        ObsVec<ObsT>::store(o + e, bits_at(l.fm, e), bits_at(l.fx, e));
-    } else {
-        for (int u = max(e, 0); u < min(e + VEC, total); ++u) o[u] = (ObsT)elem_val(bits_at(l.fm, u), bits_at(l.fx, u), 0);
-    }
-}
-
-// The G = 16 delta write.  FD is shifted by sh = (o's element index) mod VEC, so chunk boundaries are multiples of
-// VEC and no chunk straddles an FD word.  Two passes: every lane takes FD words and lists the dirty chunks of its
-// words (most words are zero) in LDS -- the agent tables' words, dead once the images are built; then the listed
-// chunks are stored one per lane, so the stores (and the bit extraction in front of each) run on dense waves.  A
-// chunk that finds the list full is stored by the lane that found it.
-template <int T, typename ObsT>
-__device__ __forceinline__ void write_obs_delta16(const EnvParams &p, const EnvLds &l, ObsT *__restrict__ o, int sh) {
-    constexpr int VEC = ObsVec<ObsT>::N;
-    const int total = p.A * p.D;
-    const int nw = (total + sh + 31) >> 5;
-    uint32_t *list = l.rel;  // rel, nbr contiguous
-    const int cap = p.A * (p.WC + p.WV);
-    int *count = &l.red[7];  // zero so far
-    for (int j = threadIdx.x; j < nw; j += T) {
-        uint32_t d = l.fd[j];
-        if (d == 0) continue;
-        // one bit per dirty chunk, at the chunk's first bit
-        if (VEC == 4) {
-            d |= d >> 1;
-            d |= d >> 2;
-            d &= 0x11111111u;
-        } else {
-            d = ((d & 0xFFFFu) ? 1u : 0u) | ((d >> 16) ? 0x10000u : 0u);
-        }
-        int slot = atomicAdd(count, __popc(d));
-        while (d) {
-            const int ec = 32 * j + __ffs(d) - 1;
-            d &= d - 1;
-            if (slot < cap)
-                list[slot] = (uint32_t)ec;
-            else
-                store_chunk16<ObsT>(p, l, o, ec, sh);
-            ++slot;
-        }
-    }
-    lds_barrier();
-    const int n = min(*count, cap);
-    for (int i = threadIdx.x; i < n; i += T) store_chunk16<ObsT>(p, l, o, (int)list[i], sh);
-#ifdef MSAT_DEBUG
-    for (int e = threadIdx.x; e < total; e += T)  // elements of clean chunks are read back
-        if ((bits_at(l.fd, (e + sh) & ~(VEC - 1)) & low_mask(VEC)) == 0) dcheck_obs_kept(l, o, e, 1);
-#endif
-}
-
 // ---------------------------------------------------------------- kernel ----
 // XCD-major env order: blocks b and b+8 share an XCD (round-robin dispatch, speed only),
 // so consecutive envs -- adjacent obs blocks in HBM -- are written through one XCD's L2.
@@ -545,6 +487,100 @@ struct ClockStamp {
         }
     }
 };
+
+__host__ __device__ __forceinline__ ObsGeom obs_geom(const EnvParams &p) {
+    return ObsGeom{p.V, p.C, p.A, p.D, p.WV, p.WC, p.base, p.rem};
+}
+
+// One listed chunk of the sparse delta write (obs_sparse.h, sparse_entry): a fast entry carries its nibbles; a slow
+// one (the chunk straddles a source word, a region, a row or an end of the block; every int8 chunk) is evaluated
+// element by element from the bit words and the agent tables.
+template <typename ObsT>
+__device__ __forceinline__ void store_sparse_entry(const EnvParams &p, const EnvLds &l, ObsT *__restrict__ o,
+                                                   uint32_t entry, int sh) {
+    constexpr int VEC = ObsVec<ObsT>::N;
+    if (VEC == 4 && (entry & kSparseFast)) {
+        ObsVec<ObsT>::store(o + (int)(((entry >> 8) & 0x7FFFFFu) * 4u) - sh, (entry >> 4) & 15u, entry & 15u);
+        return;
+    }
+    const ObsGeom g = obs_geom(p);
+    const int total = p.A * p.D, e = (int)entry - sh;
+    const int lo = max(e, 0), hi = min(e + VEC, total);
+    uint32_t m = 0, x = 0;
+    for (int u = lo; u < hi; ++u) {
+        const int v = obs_elem(g, l.x, l.sat, l.rel, l.nbr, u);
+        m |= (v >= 0 ? 1u : 0u) << (u - e);
+        x |= (v > 0 ? 1u : 0u) << (u - e);
+    }
+    if (lo == e && hi == e + VEC) {
+        ObsVec<ObsT>::store(o + e, m, x);
+    } else {
+        for (int u = lo; u < hi; ++u) o[u] = (ObsT)elem_val(m, x, u - e);
+    }
+}
+
+// The sparse G = 16 delta write: no FM / FX / FD images.  Every (agent, source word) task reads its diff word
+// (x ^ shadow x, sat ^ shadow sat) first and ends there when it is zero; the others mask it with the agent's table
+// word and list one entry per dirty chunk (sparse_task / sparse_entry) in the words the images would occupy -- the
+// agent tables stay live for the slow entries.  A chunk two tasks reach is listed by both: both stores carry the same
+// bytes.  Then the list is stored one chunk per lane on dense waves; a chunk that finds the list full is stored by
+// the lane that found it.
+template <int T, typename ObsT>
+__device__ __forceinline__ void write_obs_sparse16(const EnvParams &p, const EnvLds &l, ObsT *__restrict__ o, int sh,
+                                                   const ClockStamp *cs) {
+    constexpr int VEC = ObsVec<ObsT>::N;
+    const ObsGeom g = obs_geom(p);
+    const int U = 2 * ((p.V + 31) >> 5) + ((p.C + 31) >> 5);  // source words per row
+    uint32_t *list = l.fm;                                  // fm, fx, fd contiguous
+    const int cap = 3 * obs_image_words(p) + 1;
+    int *count = &l.red[7];  // zero so far
+    for (int t0 = 0; t0 < p.A * U; t0 += T) {  // (uniform trip count: the slot allocation below is per wave)
+        const int t = t0 + (int)threadIdx.x, i = t / U;
+        SparseTask k;
+        uint64_t d = 0;
+        if (t < p.A * U && sparse_task<VEC>(g, i, t - i * U, l.x, l.sat, l.sx, l.ssat, l.rel, l.nbr, sh, k)) d = k.dirty;
+        const int c = __popcll(d);  // <= 16 chunks under one task
+        if (__ballot(c != 0) == 0) continue;
+        // list slots: one atomic per wave (64 lanes on the one counter serialise in the LDS), and this lane's offset
+        // as the prefix sum of c over the lower lanes, bit plane by bit plane
+        int pre = 0, tot = 0;
+#pragma unroll
+        for (int b = 0; b < 5; ++b) {
+            const uint64_t m = __ballot((c >> b) & 1);
+            pre += (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) << b;
+            tot += __popcll(m) << b;
+        }
+        int base = 0;
+        if ((threadIdx.x & 63) == 0) base = atomicAdd(count, tot);
+        int slot = __builtin_amdgcn_readfirstlane(base) + pre;
+        while (d) {
+            const uint32_t entry = sparse_entry<VEC>(k, __ffsll((unsigned long long)d) - 1);
+            d &= d - 1;
+            if (slot < cap)
+                list[slot] = entry;
+            else
+                store_sparse_entry<ObsT>(p, l, o, entry, sh);
+            ++slot;
+        }
+    }
+    lds_barrier();
+    if (cs) cs->mark(4);
+    const int n = min(*count, cap);
+    for (int i = threadIdx.x; i < n; i += T) store_sparse_entry<ObsT>(p, l, o, list[i], sh);
+#ifdef MSAT_DEBUG
+    // chunks in which no element differs from the shadow row's image are read back
+    const int total = p.A * p.D;
+    for (int q = threadIdx.x; q * VEC < total + sh; q += T) {
+        const int lo = max(q * VEC - sh, 0), hi = min(q * VEC - sh + VEC, total);
+        bool dirty = false;
+        for (int e = lo; e < hi; ++e)
+            dirty |= obs_elem(g, l.x, l.sat, l.rel, l.nbr, e) != obs_elem(g, l.sx, l.ssat, l.rel, l.nbr, e);
+        if (dirty) continue;
+        for (int e = lo; e < hi; ++e)
+            MSAT_DCHECK((int)o[e] == obs_elem(g, l.x, l.sat, l.rel, l.nbr, e) ? 0 : -1 - e, 1);
+    }
+#endif
+}
 
 // The prefetch of an instance's pool row and agent tables into this lane's registers (one round trip).
 template <int T>
@@ -609,7 +645,8 @@ __device__ __forceinline__ void reset_assignment(const EnvParams &p, const EnvLd
 }
 
 // Stage instance pidx's agent tables in LDS (the first kPf* words from this lane's prefetch registers when pf),
-// build the obs bit images and stream the env's (A, D) block.
+// build the obs bit images and stream the env's (A, D) block -- or, on a delta step with 16-byte groups, list and
+// store the dirty chunks straight from the source diff (write_obs_sparse16).
 // SH: the launch has an obs shadow (shadow::env_kernel; without one the code is the plain full write).
 template <typename ObsT, int T, bool SH>
 __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const EnvLds &l, const msat_pool &pool,
@@ -621,11 +658,12 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
     // row as it was, it named this instance, and the block holds its image: store only what differs.
     const int tid = threadIdx.x;
     const int nwV = (p.V + 31) >> 5, nwC = (p.C + 31) >> 5;
-    if (SH && delta)  // source bits that changed (red[6], zero so far): many -> the plain full write
-        for (int t = tid; t < nwV + nwC; t += T) {
-            const int n = t < nwV ? __popc(l.x[t] ^ l.sx[t]) : __popc(l.sat[t - nwV] ^ l.ssat[t - nwV]);
-            if (n) atomicAdd(&l.red[6], n);
-        }
+    // a step that flipped more than a quarter of the env's variable + clause bits (red[6], counted by env_run right
+    // after the clause scan; mode-1 actions can flip them all) touches most groups anyway: the plain full write,
+    // decided before any image work
+    if (!SH || (delta && 4 * l.red[6] > p.V + p.C)) delta = false;
+    // G = 16: the sparse write from the source diff, no bit images (and none to zero)
+    const bool sparse = SH && delta && delta_g == 16;  // (a launch with a shadow is never an ablated one)
     if (SH && srow != nullptr) {
         if (tid == 0) srow[0] = (uint32_t)pidx;
         for (int t = tid; t < nwV + nwC; t += T) srow[1 + t] = t < nwV ? l.x[t] : l.sat[t - nwV];
@@ -646,24 +684,20 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
         }
         for (int t = t0r + tid; t < p.A * p.WC; t += T) l.rel[t] = rel_g[t];
         for (int t = t0n + tid; t < p.A * p.WV; t += T) l.nbr[t] = nbr_g[t];
-        for (int t = tid; t < (SH && delta ? 3 * obs_image_words(p) + 1 : 2 * obs_image_words(p)); t += T)
-            l.fm[t] = 0u;  // fm, fx, fd contiguous
+        if (!sparse)
+            for (int t = tid; t < (SH && delta ? 3 * obs_image_words(p) + 1 : 2 * obs_image_words(p)); t += T)
+                l.fm[t] = 0u;  // fm, fx, fd contiguous
     }
     lds_barrier();
     if (cs) cs->mark(3);
-    // a step that flipped more than a quarter of the env's variable + clause bits (mode-1 actions can flip them
-    // all) touches most groups anyway: the full write, without the group tests
-    if (!SH || (delta && 4 * l.red[6] > p.V + p.C)) delta = false;
-    if ((p.ablate & 3) == 0) {
-        // G = 16: FD at bit e + (o's element index mod the chunk), so that chunk k is bits [k VEC, (k + 1) VEC)
-        const int fd_shift =
-            SH && delta && delta_g == 16 ? (int)((reinterpret_cast<uintptr_t>(o) / sizeof(ObsT)) % ObsVec<ObsT>::N) : 0;
-        build_obs_images<T, SH>(p, l, delta, fd_shift);
+    if (SH && sparse) {
+        write_obs_sparse16<T, ObsT>(p, l, o, (int)((reinterpret_cast<uintptr_t>(o) / sizeof(ObsT)) % ObsVec<ObsT>::N),
+                                    cs);
+    } else if ((p.ablate & 3) == 0) {
+        build_obs_images<T, SH>(p, l, delta);
         lds_barrier();
         if (cs) cs->mark(4);
-        if (SH && delta && delta_g == 16)
-            write_obs_delta16<T, ObsT>(p, l, o, fd_shift);
-        else if (SH && delta)
+        if (SH && delta)
             write_obs_delta<T, ObsT>(p, l, o, delta_g);
         else
             write_obs<T, ObsT>(p, l, o);
@@ -813,6 +847,14 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
             eval_clauses<T, false, kPfClause>(p, l, pool.lits, pidx, scan_sat, scan_ntrue, pw);
         lds_barrier();
         cs.mark(2);
+        if (SH) {  // source bits that differ from the shadow row -> red[6] (zero so far), read after the next barrier:
+                   // the obs write's full-or-sparse decision needs nothing else
+            const int nwV = (p.V + 31) >> 5, nwC = (p.C + 31) >> 5;
+            for (int t = tid; t < nwV + nwC; t += T) {
+                const int n = t < nwV ? __popc(l.x[t] ^ l.sx[t]) : __popc(l.sat[t - nwV] ^ l.ssat[t - nwV]);
+                if (n) atomicAdd(&l.red[6], n);
+            }
+        }
         if (MODE != kModeObs && tid == 0) {
             const int u_new = l.red[0];
             const bool solved = (u_new == 0);
@@ -968,7 +1010,9 @@ env_kernel(EnvParams p, msat_pool pool, msat_env_state st, const int32_t *__rest
 // kernel's) arguments and an LDS carve that read them still cost uf50 x 1,024 and mixed x 1,024 1.9 %.
 namespace shadow {
 template <int MODE, typename ObsT, int T>
-__global__ void __launch_bounds__(T)
+// 512 lanes: 8 waves per SIMD, i.e. four resident workgroups per CU instead of three (the launch is bound by each
+// env's dependent chain); the other widths compile as without the attribute
+__global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T == 512 ? 8 : 1, 8)))
 env_kernel(EnvParams p, msat_pool pool, msat_env_state st, const int32_t *__restrict__ actions,
            const uint8_t *__restrict__ reset_mask, const int32_t *__restrict__ new_pidx,
            const uint8_t *__restrict__ new_assign, uint64_t seed, uint64_t ctr, msat_step_out out,
