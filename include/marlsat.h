@@ -29,6 +29,8 @@
  *                               src/learners/mappo_gnn_sat_learner.py:176-195
  *   msat_static_var_features <- SATDataWrapper._state_to_gnn_input degrees
  *                               src/learners/mappo_gnn_sat_learner.py:150-164
+ *   msat_walksat             <- solve_one (pysat Glucose3 -> one .sol per .cnf)  src/utils/sat_solver.py:5-29;
+ *                               here a batched WalkSAT/SKC local search
  *   msat_gae                 <- _calculate_gae + global normalisation
  *                               src/learners/mappo_gnn_sat_learner.py:504-532
  */
@@ -241,6 +243,48 @@ int msat_bc_greedy_labels(const msat_env_desc *desc, const uint16_t *lits, const
  * (Additive entry point: msat_version() stays 3, no struct changed.) */
 int msat_bc_corrupt(const uint8_t *src, int32_t n_src, const int32_t *src_row, int32_t S, int32_t V,
                     int32_t level, uint64_t seed, uint64_t counter, uint8_t *dst, void *stream);
+
+/* Batched WalkSAT/SKC on the device: the expert solutions of behavioural cloning for any CNF set (replaces
+ * src/utils/sat_solver.py, which runs pysat's Glucose3 over a directory), and the classical local-search
+ * baseline beside the learned policy.  Sample s of S runs instance clamp(problem_idx[s], 0, N-1) of the packed
+ * pool lits (N,C,4).  Every decision depends only on the current assignment and the Philox stream, so a host
+ * replay reproduces the outputs bit for bit.
+ *   Clause truth is the env's: a code c < MSAT_LIT_ABSENT is true iff (x[c >> 1] ^ c) & 1; MSAT_LIT_NULL is
+ *   always false; MSAT_LIT_ABSENT slots are inert.  The real slots of a clause are those with a code below
+ *   MSAT_LIT_ABSENT, in slot order 0, 1, 2.
+ *   Start: init_assign NULL: x is the assignment msat_env_reset draws for env s at (seed, counter) (block
+ *   1 + v/128 of the reset stream, word (v%128)/32, bit v%32); otherwise x = init_assign[s] & 1 ((S,V) u8).
+ *   Step t = 0, 1, ...:
+ *    1. U = the unsatisfied clauses in ascending clause index, n = |U|.  n == 0: stop, solved = 1, flips = t.
+ *       t == max_flips: stop, solved = 0, flips = t.
+ *    2. q = philox4x32_10((counter lo, counter hi, s, 0x80000000 + t), seed lo, seed hi), words q0, q1, q2
+ *       (the reset blocks use c3 = 0 .. 1 + V/128, so the two ranges never meet).
+ *    3. The clause U[(q0 * n) >> 32]; its candidates are its real slots j = 0..m-1 with variable v_j.  m == 0
+ *       (null literals only): nothing flips, t advances.
+ *    4. break_j = the number of clauses satisfied now and unsatisfied after flipping v_j alone (a clause breaks
+ *       iff its set of true slots is non-empty and equals its set of slots on v_j).
+ *    5. b = min_j break_j.  b == 0 or q1 >= noise_p32: flip the first slot with break_j == b; otherwise flip
+ *       slot (q2 * m) >> 32.
+ *   Outputs per sample: assign_out (S,V) u8 the final x, solved (S,) u8, flips (S,) i32, num_unsat (S,) i32 the
+ *   final n.
+ * form: 0 picks the kernel form (registers up to 256 clauses, then form 6 where it fits, else 3, 4 or 5);
+ * 1..msat_walksat_forms() force one.  Forms 1..4 keep 2 / 4 / 8 / 16 clauses per lane in registers
+ * (num_clauses <= 128 / 256 / 512 / 1023); form 5 walks the LDS copy of the instance and takes any num_clauses;
+ * form 6 keeps per-variable clause lists, break counts and an unsatisfied-clause bitmap in LDS, so that a flip
+ * touches only the clauses of its variable.  All forms give the same outputs.  Every form needs
+ * 8 * num_clauses + num_vars (rounded up to 16) <= 65536 bytes of LDS per sample; form 6 needs
+ * 14 * num_clauses + 8 * ceil(num_clauses / 64) + 9 * num_vars + 4 (rounded up to 16) <= 65536 and is refused
+ * when forced on a larger shape (form 0 then takes another form).
+ * Enqueues only.  num_samples == 0: MSAT_OK without a launch.  MSAT_EBADARG: a NULL pointer (init_assign
+ * excepted) with num_samples > 0, num_vars outside [1, 32000], num_clauses < 1, num_problems < 1, max_flips < 0,
+ * num_samples < 0, form outside 0..msat_walksat_forms(), a forced form that cannot hold num_clauses, a shape
+ * past the LDS bound.
+ * (Additive entry points: msat_version() stays 3, no struct changed.) */
+int msat_walksat(const uint16_t *lits, int32_t num_problems, int32_t num_vars, int32_t num_clauses,
+                 const int32_t *problem_idx, int32_t num_samples, const uint8_t *init_assign,
+                 int32_t max_flips, uint32_t noise_p32, uint64_t seed, uint64_t counter, int32_t form,
+                 uint8_t *assign_out, uint8_t *solved, int32_t *flips, int32_t *num_unsat, void *stream);
+int msat_walksat_forms(void); /* number of kernel forms; form 0 = automatic, 1..n force one */
 
 /* Single-agent SatEnv clause features [is_sat, is_unsat, 1] (B,C,3) (src/envs/sat_env.py:143-160). */
 int msat_clause_sat_features(const msat_env_desc *desc, const msat_env_state *state,

@@ -108,6 +108,12 @@ def _load():
         "msat_clause_sat_features": (c_int32, [POINTER(EnvDesc), POINTER(EnvStateC), P, P]),
         "msat_bc_greedy_labels": (c_int32, [POINTER(EnvDesc), P, P, P, c_float, P, P, P]),
         "msat_bc_corrupt": (c_int32, [P, c_int32, P, c_int32, c_int32, c_int32, c_uint64, c_uint64, P, P]),
+        "msat_walksat": (
+            c_int32,
+            [P, c_int32, c_int32, c_int32, P, c_int32, P, c_int32, ctypes.c_uint32, c_uint64, c_uint64, c_int32, P, P,
+             P, P, P],
+        ),
+        "msat_walksat_forms": (c_int32, []),
         "msat_static_var_features": (c_int32, [P, c_int32, c_int32, c_int32, P, P]),
         "msat_reset_queue_words": (c_size_t, [c_int32]),
         "msat_env_launch_threads": (c_int32, [POINTER(EnvDesc)]),
@@ -299,6 +305,8 @@ EXPORTED = (
     "msat_clause_sat_features",
     "msat_bc_greedy_labels",
     "msat_bc_corrupt",
+    "msat_walksat",
+    "msat_walksat_forms",
     "msat_env_step_grouped",
     "msat_env_obs",
     "msat_env_masks",

@@ -129,7 +129,23 @@ def bc_settings(config: Optional[dict]) -> Dict:
             "CORRUPTION_LEVEL": int(bc.get("CORRUPTION_LEVEL", 3)),
             "TAU_IMPROVE": float(bc.get("TAU_IMPROVE", 0.0)),
             "SOL_DATA_DIR": bc.get("SOL_DATA_DIR", "data/uf20-91-answer"),
+            "SOLVE_MISSING_EXPERTS": bool(bc.get("SOLVE_MISSING_EXPERTS", False)),
             "SAVE_PATH": bc.get("SAVE_PATH", "models/bc_pretrained")}
+
+
+def solve_missing_experts(cnf_dir: str, sol_dir: str, seed: int = 0, log=print) -> Dict[str, List[str]]:
+    """bc_training.SOLVE_MISSING_EXPERTS: WalkSAT on the device (utils.sat_solver.solve_directory) for the
+    ``.cnf`` files of cnf_dir that have no ``.sol`` in sol_dir; the files that have one are left alone."""
+    from ..utils.sat_solver import sol_path, solve_directory
+
+    names = sorted(f for f in os.listdir(cnf_dir) if f.endswith(".cnf"))
+    missing = [n for n in names if not os.path.exists(sol_path(sol_dir, n))]
+    res = {"solved": [], "unsolved": []}
+    if missing:
+        res = solve_directory(cnf_dir, sol_dir, names=missing, key=PRNGKey(seed))
+    log(f"[*] experts: {len(names) - len(missing)} .sol files found, {len(res['solved'])} solved by WalkSAT, "
+        f"{len(res['unsolved'])} skipped (unsolved)")
+    return res
 
 
 def preprocess(expert_data: List[Dict[str, np.ndarray]], env: SATEnv, config: Optional[dict] = None,
@@ -181,6 +197,8 @@ def run(config: Dict, log=print) -> Dict:
                  action_mode=fc.get("action_mode", 0), r_clause=rewards.get("R_CLAUSE", 0.02),
                  r_sat=rewards.get("R_SAT", 1.0), gamma=fc.get("GAMMA", 0.99))
     cnf_dir = config.get("CNF_DATA_DIR", "data")
+    if bc["SOLVE_MISSING_EXPERTS"]:
+        solve_missing_experts(cnf_dir, bc["SOL_DATA_DIR"], seed, log)
     experts = load_expert_data(cnf_dir, bc["SOL_DATA_DIR"])
     if not experts:
         log(f"no expert (.cnf, .sol) pairs found in {cnf_dir} / {bc['SOL_DATA_DIR']}")

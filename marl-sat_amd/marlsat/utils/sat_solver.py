@@ -1,0 +1,95 @@
+"""Expert solutions for a directory of CNF files -- stands in for src/utils/sat_solver.py.
+
+    python -m marlsat.utils.sat_solver --cnf-dir data/uf50-218 --sol-dir data/uf50-218-answer
+
+The reference runs pysat's Glucose3 over every ``.cnf`` and writes ``<stem>.sol`` as ``' '.join(map(str, assign))``
+(one line of 0/1 values, ``sat_solver.py:5-29``).  Here the files are grouped by (num_vars, num_clauses), each
+group becomes one device problem pool, and ``solvers.walksat.solve_pool`` (batched WalkSAT/SKC with random
+restarts, ``msat_walksat``) searches all of its instances at once.  Every solution is verified with
+``SATEnv._calculate_satisfaction_explicit`` before its file is written, in the reference's format, which
+``runners.behavioral_cloning.load_expert_data`` reads as is.  Local search is incomplete: an instance it does not
+solve (an unsatisfiable one never is) gets no file and is reported as unsolved.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+
+from .data_parser import group_problems, load_cnf_problems
+
+
+def sol_path(sol_dir: str, cnf_name: str) -> str:
+    stem = cnf_name[: -len(".cnf")] if cnf_name.endswith(".cnf") else cnf_name
+    return os.path.join(sol_dir, stem + ".sol")
+
+
+def write_sol(path: str, assignment) -> None:
+    """One line of space-separated 0/1 values (the reference's ``' '.join(map(str, assign))``)."""
+    with open(path, "w") as f:
+        f.write(" ".join(str(int(v)) for v in np.asarray(assignment).reshape(-1)) + "\n")
+
+
+def solve_directory(cnf_dir: str, sol_dir: str, *, names: Optional[Sequence[str]] = None, log=None,
+                    **solve_kwargs) -> Dict[str, List[str]]:
+    """Solve the ``.cnf`` files of ``cnf_dir`` (all of them, or only ``names``) and write ``<stem>.sol`` into
+    ``sol_dir`` for each one solved.  ``solve_kwargs`` go to ``solve_pool`` (tries, max_flips, max_rounds, noise,
+    key).  Returns ``{"solved": [names], "unsolved": [names]}`` in directory order."""
+    from ..envs.multi_agent_sat_env import SATEnv
+    from ..solvers.walksat import solve_pool
+
+    problems = load_cnf_problems(cnf_dir)
+    if names is not None:
+        keep = set(names)
+        problems = [p for p in problems if p["name"] in keep]
+    os.makedirs(sol_dir, exist_ok=True)
+    done = {}
+    for (V, C), g in group_problems(problems).items():
+        env = SATEnv(V, C, max_steps=1, vars_per_agent=V)  # one agent: only the clause check is used
+        pool = env.make_pool(g["clauses"])
+        res = solve_pool(pool, **solve_kwargs)
+        _, nun = env._calculate_satisfaction_explicit(res["solution"], g["clauses"])
+        valid = res["solved"] & (nun.cpu().numpy() == 0)
+        if (res["solved"] & ~valid).any():
+            bad = [n for n, s, v in zip(g["names"], res["solved"], valid) if s and not v]
+            raise RuntimeError(f"walksat reported solutions that do not satisfy their formulas: {bad}")
+        for name, ok, x in zip(g["names"], valid, res["solution"]):
+            done[name] = bool(ok)
+            if ok:
+                write_sol(sol_path(sol_dir, name), x)
+        if log is not None:
+            log(f"V={V} C={C}: {int(valid.sum())} / {len(valid)} solved")
+    order = [p["name"] for p in problems]
+    return {"solved": [n for n in order if done[n]], "unsolved": [n for n in order if not done[n]]}
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description="WalkSAT on the device: one .sol per .cnf of a directory")
+    ap.add_argument("--cnf-dir", required=True)
+    ap.add_argument("--sol-dir", required=True)
+    ap.add_argument("--tries", type=int, default=8, help="samples per unsolved instance and round")
+    ap.add_argument("--max-flips", type=int, default=100_000, help="flips per sample and launch")
+    ap.add_argument("--max-rounds", type=int, default=4, help="restart rounds")
+    ap.add_argument("--noise", type=float, default=0.5, help="random-walk probability")
+    ap.add_argument("--seed", type=int, default=0)
+    return ap
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    from ..random import PRNGKey
+
+    a = build_parser().parse_args(argv)
+    res = solve_directory(a.cnf_dir, a.sol_dir, tries=a.tries, max_flips=a.max_flips, max_rounds=a.max_rounds,
+                          noise=a.noise, key=PRNGKey(a.seed), log=print)
+    print(f"solved {len(res['solved'])}, unsolved {len(res['unsolved'])} of "
+          f"{len(res['solved']) + len(res['unsolved'])} files in {a.cnf_dir}; solutions in {a.sol_dir}")
+    for n in res["unsolved"]:
+        print(f"unsolved: {n}")
+    return 1 if res["unsolved"] else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
