@@ -458,8 +458,10 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 //   [0] shader-clock counter delta over the workgroup's run (s_memtime), [1] the 100 MHz real-time counter
 //   delta (s_memrealtime): clock MHz = 100 [0] / [1];
 //   [2] real time at the workgroup's start, [3..6] at four phase ends (3: assignment bits + flips in LDS,
-//   i.e. the first global loads landed; 4: clause scan done; 5: agent tables staged; 6: obs bit images
-//   built), [7] at the end, after wave 0's stores have drained (vmcnt(0)).
+//   i.e. the first global loads landed; 4: clause scan done; 5: agent tables staged -- the span from 4 holds wave
+//   0's own decision and transition outputs, the write-backs and the staging, no longer a barrier that waits for
+//   lane 0; 6: obs bit images built, or the sparse write's chunks listed), [7] at the end, after wave 0's stores
+//   have drained (vmcnt(0)).
 // Same CU, same wave: the ratio is the clock that CU ran at while it stepped this env, and the phase times
 // are wave 0's view of the env's dependent chain.
 struct ClockStamp {
@@ -653,15 +655,15 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
                                                     int pidx, bool pf, const uint32_t (&prel)[kPfRel],
                                                     const uint32_t (&pnbr)[kPfNbr], ObsT *__restrict__ o,
                                                     const ClockStamp *cs, uint32_t *__restrict__ srow, bool delta,
-                                                    int delta_g) {
+                                                    int delta_g, int ndiff) {
     // srow: the env's obs shadow row (NULL: none), rewritten to describe this write.  delta: l.sx / l.ssat hold the
     // row as it was, it named this instance, and the block holds its image: store only what differs.
     const int tid = threadIdx.x;
     const int nwV = (p.V + 31) >> 5, nwC = (p.C + 31) >> 5;
-    // a step that flipped more than a quarter of the env's variable + clause bits (red[6], counted by env_run right
+    // a step that flipped more than a quarter of the env's variable + clause bits (ndiff, counted by env_run right
     // after the clause scan; mode-1 actions can flip them all) touches most groups anyway: the plain full write,
     // decided before any image work
-    if (!SH || (delta && 4 * l.red[6] > p.V + p.C)) delta = false;
+    if (!SH || (delta && 4 * ndiff > p.V + p.C)) delta = false;
     // G = 16: the sparse write from the source diff, no bit images (and none to zero)
     const bool sparse = SH && delta && delta_g == 16;  // (a launch with a shadow is never an ablated one)
     if (SH && srow != nullptr) {
@@ -709,6 +711,18 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
 }
 
 // One environment (index b of its batch) advanced / reset / observed by one workgroup.
+//
+// Workgroup barriers, by path (every wave of a workgroup takes the same path: each condition below is a function of
+// launch parameters, uniformly loaded words and LDS words that are final since the previous barrier):
+//   running step   B1 assignment bits | B2 flips | B3 clause scan | B5 tables staged | B6 images built or chunks listed
+//   covered        B1 | B2 | B3 | R0 before the reset rewrites l.x | R1 new assignment bits, then the write-back; no obs
+//   in-workgroup   B1 | B2 | B3 | R0 before l.x is rewritten and red[0..1] zeroed | R2 new assignment bits |
+//   reset                        R3 its clause scan | B5 | B6
+//   reset mode     R2 | R3 | B5 | B6               (msat_env_reset: no step in front)
+//   obs only       B1 | B2 | B3 | B5 | B6          (no flips between B1 and B2, no state written)
+//   reset workgroup (env_side_reset)  the rank scan | assignment bits | clause scan | B5 | B6
+// After B3 nothing is broadcast: every wave reads red[0] (unsat count) and red[3] (covered) and derives done, the
+// reset decision and, with a shadow, the diff count itself, so no wave waits for lane 0's transition outputs.
 template <int MODE, typename ObsT, int T, bool SH = false>
 __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &pool, const msat_env_state &st,
                                         const int32_t *__restrict__ actions, const uint8_t *__restrict__ reset_mask,
@@ -732,6 +746,7 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
     }
 
     bool do_reset = (MODE == kModeReset);
+    int ndiff = 0;  // SH: source bits that differ from the shadow row (a stepped env that does not reset)
     // the per-lane loads that do not depend on problem_idx, issued together with it (one round trip): this
     // lane's action and its assignment byte of the first ballot pass (clamped indices, no branches), then
     // problem_idx, step and unsat.  (step / unsat are wave-uniform values the compiler moves to scalar registers
@@ -847,20 +862,28 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
             eval_clauses<T, false, kPfClause>(p, l, pool.lits, pidx, scan_sat, scan_ntrue, pw);
         lds_barrier();
         cs.mark(2);
-        if (SH) {  // source bits that differ from the shadow row -> red[6] (zero so far), read after the next barrier:
-                   // the obs write's full-or-sparse decision needs nothing else
+        // ---- the decision, taken by every wave for itself from what the scan's barrier published (red[0], red[3])
+        // and the uniformly loaded step0: nothing is broadcast, nobody waits for lane 0's transition outputs
+        const int u_new = MODE != kModeObs ? __builtin_amdgcn_readfirstlane(l.red[0]) : 0;
+        const bool solved = (u_new == 0);
+        // single-agent SatEnv (sat_env.py:106) tests the pre-increment step
+        const bool done = solved || (p.reward_mode == MSAT_REWARD_SINGLE_DELTA ? step0 >= p.max_steps
+                                                                               : step0 + 1 >= p.max_steps);
+        // a covered env times out now (the previous launch listed it at max_steps - 1): its reset happens in any
+        // case, here and in its reset workgroup, so the state stays whole even for a misused queue
+        const bool reset_now = (MODE == kModeStepAutoReset) && (done || covered);
+        do_reset = reset_now;
+        if (SH && !do_reset) {  // source bits that differ from the shadow row: the obs write's full-or-sparse decision
+                                // needs nothing else.  Each wave sums the nwV + nwC diff words itself (shuffles)
             const int nwV = (p.V + 31) >> 5, nwC = (p.C + 31) >> 5;
-            for (int t = tid; t < nwV + nwC; t += T) {
-                const int n = t < nwV ? __popc(l.x[t] ^ l.sx[t]) : __popc(l.sat[t - nwV] ^ l.ssat[t - nwV]);
-                if (n) atomicAdd(&l.red[6], n);
-            }
+            int n = 0;
+            for (int t = tid & 63; t < nwV + nwC; t += 64)
+                n += t < nwV ? __popc(l.x[t] ^ l.sx[t]) : __popc(l.sat[t - nwV] ^ l.ssat[t - nwV]);
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d, 64);
+            ndiff = n;
         }
         if (MODE != kModeObs && tid == 0) {
-            const int u_new = l.red[0];
-            const bool solved = (u_new == 0);
-            // single-agent SatEnv (sat_env.py:106) tests the pre-increment step
-            const bool done = solved || (p.reward_mode == MSAT_REWARD_SINGLE_DELTA ? step0 >= p.max_steps
-                                                                                   : step0 + 1 >= p.max_steps);
             float r;
             if (p.reward_mode == MSAT_REWARD_SINGLE_DELTA) {
                 // sat_env.py:86-101, f32 in the reference's order: ((u_prev - u_new) * 10 + bonus) + (-0.005)
@@ -881,11 +904,7 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
             out.solved[b] = solved ? 1 : 0;
             if (out.num_unsat) out.num_unsat[b] = u_new;
             if (out.episode_step) out.episode_step[b] = step0 + 1;
-            // a covered env times out now (the previous launch listed it at max_steps - 1): its reset happens in any
-            // case, here and in its reset workgroup, so the state stays whole even for a misused queue
             MSAT_DCHECK(covered && !done ? 1 : 0, 1);
-            const bool reset_now = (MODE == kModeStepAutoReset) && (done || covered);
-            l.red[2] = reset_now ? 1 : 0;
             if (!reset_now) {
                 st.num_unsat[b] = u_new;
                 st.step[b] = step0 + 1;
@@ -897,12 +916,15 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
                     next_step + 1 >= p.max_steps ? rq_token(p.rq_serial + 1u) : 0u;
             }
         }
-        lds_barrier();
-        do_reset = (l.red[2] != 0);
     }
 
     if (do_reset) {
         // ---- reset (env:158-181): new problem, new assignment ---------------
+        // A stepped env that resets here: slower waves may still be reading red[0] / red[3] (their decision) and l.x;
+        // the reset rewrites l.x and zeroes red[0..1], so it waits for them first.  Uniform: do_reset is a function of
+        // red[0], red[3] (both final since the scan's barrier, neither written before this one), step0 and the
+        // launch's parameters, the same values in every wave.
+        if (MODE != kModeReset) lds_barrier();
         pidx = reset_instance(p, new_pidx, seed, ctr, b);
         if (MSAT_DEBUG_BUILD && tid == 0) MSAT_DCHECK(pidx, p.N);  // the reset's pool row
         reset_assignment<T>(p, l, new_assign, seed, ctr, b);
@@ -918,7 +940,7 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
             for (int v = tid; v < p.V; v += T) xg[v] = (uint8_t)bit(l.x, v);
             return;
         }
-        if (tid < 2) l.red[tid] = 0;  // red[2] (reset broadcast) may still be read by slower waves
+        if (tid < 2) l.red[tid] = 0;  // (every wave has read them: the barrier above)
         lds_barrier();
         eval_clauses<T, false, 0>(p, l, pool.lits, pidx, sat_g, ntrue_g, pw);
         lds_barrier();
@@ -937,7 +959,7 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
     const bool delta = SH && (MODE == kModeStep || MODE == kModeStepAutoReset) && sa.g != 0 && !do_reset &&
                        l.red[5] == pidx;
     stage_and_write_obs<ObsT, T, SH>(p, l, pool, pidx, (MODE != kModeReset) && !do_reset, prel, pnbr,
-                                     obs + (size_t)b * p.A * p.D, &cs, srow, delta, sa.g);
+                                     obs + (size_t)b * p.A * p.D, &cs, srow, delta, sa.g, ndiff);
 }
 
 // A reset workgroup of an autoreset launch with a reset queue (rq_mode 1): the pending env of rank j, i.e. an env that
@@ -977,7 +999,7 @@ __device__ __forceinline__ void env_side_reset(const EnvParams &p, const msat_po
     if ((p.ablate & 3) == 2 || obs == nullptr) return;
     // the whole block and a fresh shadow row (its step workgroup touches neither)
     stage_and_write_obs<ObsT, T, SH>(p, l, pool, pidx, true, prel, pnbr, obs + (size_t)b * p.A * p.D, nullptr,
-                                     SH ? sa.rows + (size_t)b * shadow_row_words(p) : nullptr, false, 0);
+                                     SH ? sa.rows + (size_t)b * shadow_row_words(p) : nullptr, false, 0, 0);
 }
 
 template <int MODE, typename ObsT, int T>
