@@ -221,6 +221,11 @@ int msat_env_step_grouped(int32_t num_groups, const msat_env_desc *descs, const 
  * (Additive entry points: msat_version() stays 3, no struct changed.) */
 int msat_env_launch_threads(const msat_env_desc *desc);
 int msat_env_group_launch_threads(int32_t total_envs);
+/* The same for msat_env_step_delta, whose launches (the step kernel with the obs shadow compiled in) follow a width
+ * rule of their own: for num_agents * (2 num_vars + num_clauses) >= 16384 with int32 observations, the shapes the
+ * delta write is the default of, chosen for that kernel; for every other desc msat_env_launch_threads' value.
+ * MARLSAT_ENV_THREADS forces both.  (Additive as well: msat_version() stays 3.) */
+int msat_env_delta_launch_threads(const msat_env_desc *desc);
 
 /* obs may be NULL in msat_env_reset / msat_env_step: state-only update, no observation write
  * (the single-agent SatEnv observes the GNN input instead, src/envs/sat_env.py:120-166). */

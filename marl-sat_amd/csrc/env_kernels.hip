@@ -1,6 +1,7 @@
 // Batched multi-agent SAT environment on gfx950.
 //
-// One workgroup (64 / 256 / 512 lanes by instance size, env_threads) owns one environment for the whole call:
+// One workgroup (64 .. 512 lanes by instance and batch size: env_threads, env_delta_threads for a launch with an obs
+// shadow) owns one environment for the whole call:
 //   1. assignment -> LDS bit words (one ballot per 64 vars), agents' flips as
 //      LDS atomic XORs;
 //   2. every clause evaluated once from the L2/MALL-resident packed pool
@@ -460,7 +461,7 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 //   [2] real time at the workgroup's start, [3..6] at four phase ends (3: assignment bits + flips in LDS,
 //   i.e. the first global loads landed; 4: clause scan done; 5: agent tables staged -- the span from 4 holds wave
 //   0's own decision and transition outputs, the write-backs and the staging, no longer a barrier that waits for
-//   lane 0; 6: obs bit images built, or the sparse write's chunks listed), [7] at the end, after wave 0's stores
+//   lane 0; 6: obs bit images built, or the sparse write's task loop done, its stores issued), [7] at the end, after wave 0's stores
 //   have drained (vmcnt(0)).
 // Same CU, same wave: the ratio is the clock that CU ran at while it stepped this env, and the phase times
 // are wave 0's view of the env's dependent chain.
@@ -523,52 +524,49 @@ __device__ __forceinline__ void store_sparse_entry(const EnvParams &p, const Env
 
 // The sparse G = 16 delta write: no FM / FX / FD images.  Every (agent, source word) task reads its diff word
 // (x ^ shadow x, sat ^ shadow sat) first and ends there when it is zero; the others mask it with the agent's table
-// word and list one entry per dirty chunk (sparse_task / sparse_entry) in the words the images would occupy -- the
-// agent tables stay live for the slow entries.  A chunk two tasks reach is listed by both: both stores carry the same
-// bytes.  Then the list is stored one chunk per lane on dense waves; a chunk that finds the list full is stored by
-// the lane that found it.
+// word and store their dirty chunks themselves, one sparse_entry at a time (sparse_task / sparse_entry) -- the agent
+// tables stay live for the slow entries.  A chunk two tasks reach is stored by both: both stores carry the same
+// bytes.  (Until round 10 the tasks listed their chunks in LDS and, behind a barrier, a second pass stored the list one
+// chunk per lane: dense stores on 8 waves, but a prefix sum, an atomic, a barrier and a pass more per env; at 4 waves
+// per workgroup storing in place is the faster form)
+#ifndef MSAT_TASK_CARRY  // 0: A/B builds only (make ab)
+#define MSAT_TASK_CARRY 1
+#endif
 template <int T, typename ObsT>
 __device__ __forceinline__ void write_obs_sparse16(const EnvParams &p, const EnvLds &l, ObsT *__restrict__ o, int sh,
                                                    const ClockStamp *cs) {
     constexpr int VEC = ObsVec<ObsT>::N;
     const ObsGeom g = obs_geom(p);
     const int U = 2 * ((p.V + 31) >> 5) + ((p.C + 31) >> 5);  // source words per row
-    uint32_t *list = l.fm;                                  // fm, fx, fd contiguous
-    const int cap = 3 * obs_image_words(p) + 1;
-    int *count = &l.red[7];  // zero so far
-    for (int t0 = 0; t0 < p.A * U; t0 += T) {  // (uniform trip count: the slot allocation below is per wave)
-        const int t = t0 + (int)threadIdx.x, i = t / U;
+    // int32: (agent, source word) carried from pass to pass (obs_sparse.h): one division per lane instead of one per
+    // lane and pass (five passes of 256 lanes at uf200).  int8 keeps the division: the carried pair cost
+    // shadow::env_kernel<2, int8, 256 / 512> a spilled VGPR (8 B of scratch per lane; profiles/r10/resource_usage.txt)
+    constexpr bool kCarry = MSAT_TASK_CARRY && VEC == 4;
+    const TaskIdx stride = task_stride(T, U);
+    TaskIdx ti = task_first((int)threadIdx.x, U);
+    for (int t0 = 0; t0 < p.A * U; t0 += T) {
+        int i, s;
+        bool live;
+        if constexpr (kCarry) {
+            i = ti.i, s = ti.s;
+            live = i < p.A;
+            task_advance(ti, stride, U);
+        } else {
+            const int t = t0 + (int)threadIdx.x;
+            i = t / U, s = t - i * U;
+            live = t < p.A * U;
+        }
         SparseTask k;
         uint64_t d = 0;
-        if (t < p.A * U && sparse_task<VEC>(g, i, t - i * U, l.x, l.sat, l.sx, l.ssat, l.rel, l.nbr, sh, k)) d = k.dirty;
-        const int c = __popcll(d);  // <= 16 chunks under one task
-        if (__ballot(c != 0) == 0) continue;
-        // list slots: one atomic per wave (64 lanes on the one counter serialise in the LDS), and this lane's offset
-        // as the prefix sum of c over the lower lanes, bit plane by bit plane
-        int pre = 0, tot = 0;
-#pragma unroll
-        for (int b = 0; b < 5; ++b) {
-            const uint64_t m = __ballot((c >> b) & 1);
-            pre += (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) << b;
-            tot += __popcll(m) << b;
-        }
-        int base = 0;
-        if ((threadIdx.x & 63) == 0) base = atomicAdd(count, tot);
-        int slot = __builtin_amdgcn_readfirstlane(base) + pre;
+        if (live && sparse_task<VEC>(g, i, s, l.x, l.sat, l.sx, l.ssat, l.rel, l.nbr, sh, k)) d = k.dirty;
+        // <= 16 chunks under one task (a dead task falls through with d = 0: skipping the loop with `continue`
+        // compiled the int8 kernels at 256 / 512 lanes with a spilled VGPR)
         while (d) {
-            const uint32_t entry = sparse_entry<VEC>(k, __ffsll((unsigned long long)d) - 1);
+            store_sparse_entry<ObsT>(p, l, o, sparse_entry<VEC>(k, __ffsll((unsigned long long)d) - 1), sh);
             d &= d - 1;
-            if (slot < cap)
-                list[slot] = entry;
-            else
-                store_sparse_entry<ObsT>(p, l, o, entry, sh);
-            ++slot;
         }
     }
-    lds_barrier();
     if (cs) cs->mark(4);
-    const int n = min(*count, cap);
-    for (int i = threadIdx.x; i < n; i += T) store_sparse_entry<ObsT>(p, l, o, list[i], sh);
 #ifdef MSAT_DEBUG
     // chunks in which no element differs from the shadow row's image are read back
     const int total = p.A * p.D;
@@ -714,7 +712,8 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
 //
 // Workgroup barriers, by path (every wave of a workgroup takes the same path: each condition below is a function of
 // launch parameters, uniformly loaded words and LDS words that are final since the previous barrier):
-//   running step   B1 assignment bits | B2 flips | B3 clause scan | B5 tables staged | B6 images built or chunks listed
+//   running step   B1 assignment bits | B2 flips | B3 clause scan | B5 tables staged | B6 images built (a sparse
+//                  delta step has no B6: its tasks store their chunks themselves)
 //   covered        B1 | B2 | B3 | R0 before the reset rewrites l.x | R1 new assignment bits, then the write-back; no obs
 //   in-workgroup   B1 | B2 | B3 | R0 before l.x is rewritten and red[0..1] zeroed | R2 new assignment bits |
 //   reset                        R3 its clause scan | B5 | B6
@@ -1030,11 +1029,17 @@ env_kernel(EnvParams p, msat_pool pool, msat_env_state st, const int32_t *__rest
 // apart, they run the code they ran before.  The shadow's pointer and group size are arguments of this kernel alone
 // (ObsShadowArg), not EnvParams fields: 16 more bytes in every env kernel's (and eight times that in the grouped
 // kernel's) arguments and an LDS carve that read them still cost uf50 x 1,024 and mixed x 1,024 1.9 %.
+#ifndef MSAT_SHADOW_W8_MIN_T
+#define MSAT_SHADOW_W8_MIN_T 256
+#endif
 namespace shadow {
 template <int MODE, typename ObsT, int T>
-// 512 lanes: 8 waves per SIMD, i.e. four resident workgroups per CU instead of three (the launch is bound by each
-// env's dependent chain); the other widths compile as without the attribute
-__global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T == 512 ? 8 : 1, 8)))
+// 256 and 512 lanes (the widths env_delta_threads picks for the shapes this write is the default of): 8 waves per
+// SIMD, i.e. eight resident 256-lane workgroups per CU instead of seven, four 512-lane ones instead of three (the
+// launch is bound by how many dependent chains a CU runs one after the other); without scratch
+// for either ObsT (profiles/r10/resource_usage.txt).  64 and 128 lanes compile as without the attribute.
+// MSAT_SHADOW_W8_MIN_T: A/B builds only (make ab)
+__global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T >= MSAT_SHADOW_W8_MIN_T ? 8 : 1, 8)))
 env_kernel(EnvParams p, msat_pool pool, msat_env_state st, const int32_t *__restrict__ actions,
            const uint8_t *__restrict__ reset_mask, const int32_t *__restrict__ new_pidx,
            const uint8_t *__restrict__ new_assign, uint64_t seed, uint64_t ctr, msat_step_out out,
@@ -1426,16 +1431,25 @@ static int check_pool(const msat_pool *pool) {
     return MSAT_OK;
 }
 
-// Workgroup size of the single-class env kernel: one wave per env for small instances (more envs
-// resident per CU: the per-env chain of dependent memory round trips, not bandwidth, bounds them),
-// 512 lanes for large ones (A * D >= 16384: uf200), 256 otherwise.  MARLSAT_ENV_THREADS (64 / 128 / 256 / 512) overrides.
-static int env_threads(const EnvParams &p) {
+// MARLSAT_ENV_THREADS (64 / 128 / 256 / 512), read once per process: forces both width rules below; 0 if unset
+static int env_threads_forced() {
     static const int forced = [] {
         const char *e = getenv("MARLSAT_ENV_THREADS");
         const int v = e ? atoi(e) : 0;
         return v == 64 || v == 128 || v == 256 || v == 512 ? v : 0;
     }();
-    if (forced) return forced;
+    return forced;
+}
+
+// Workgroup size of the single-class env kernel.  Two rules, MARLSAT_ENV_THREADS overriding both:
+//  - env_threads: the launches WITHOUT an obs shadow (the full observation write; msat_env_launch_threads, the bench
+//    line's roofline.kernel label).  One wave per env for small instances (more envs resident per CU: the per-env
+//    chain of dependent memory round trips, not bandwidth, bounds them), 512 lanes for large ones (A * D >= 16384:
+//    uf200), 256 otherwise.
+//  - env_delta_threads: the launches WITH an obs shadow (shadow::env_kernel; msat_env_delta_launch_threads).  Where
+//    the delta write is the default (A * D >= 16384, int32) a width of its own; everywhere else env_threads.
+static int env_threads(const EnvParams &p) {
+    if (const int forced = env_threads_forced()) return forced;
     // Fewer lanes per env as the batch grows (more envs resident per CU), more while each env's chain bounds the
     // launch (a few envs per CU).  uf50: x 1024 7.57 us at 128 vs 7.86 at 64, 7.88 at 256; x 2048 9.86 at 64 vs 10.1
     // at 128; x 4096 14.1 at 64 vs 16.6 at 128.  uf100: x 1024 11.0 at 256 vs 11.6 at 128, 14.6 at 64; x 2048 15.3 at
@@ -1445,6 +1459,17 @@ static int env_threads(const EnvParams &p) {
     if (n >= 16384) return 512;
     if (n > 4096) return p.B <= 1024 ? 256 : 128;
     return p.B <= 1024 ? 128 : 64;
+}
+
+// A delta launch moves a fraction of the full write's bytes and is bound by how many of its workgroups' dependent
+// chains a CU runs one after the other: 256 lanes at 8 waves per SIMD hold 8 envs per CU where 512 lanes hold 4
+// (uf200 x 4096: 16 step workgroups per CU in two rounds instead of four; figures: DESIGN.md section 4, round 10,
+// profiles/r10/ab_widths.txt).  int8 and the shapes below A * D = 16384 (forced delta) were not measured: they keep
+// the plain rule's width.
+static int env_delta_threads(const EnvParams &p, int obs_dtype) {
+    if (const int forced = env_threads_forced()) return forced;
+    if ((long)p.A * p.D >= 16384 && obs_dtype == MSAT_OBS_I32) return 256;
+    return env_threads(p);
 }
 
 template <int MODE>
@@ -1466,7 +1491,7 @@ static int launch_env(const EnvParams &p, const msat_env_desc *d, const msat_poo
     msat_step_out o{};
     if (out) o = *out;
     if (p.B == 0) return MSAT_OK;
-    const int T = env_threads(p);
+    const int T = sa.rows != nullptr ? env_delta_threads(p, d->obs_dtype) : env_threads(p);
     set_dbg_extents(&pd, st, actions, obs, d->obs_dtype);
     if (int rc = set_reset_queue(&pd, st, MODE)) return rc;
     // the reset workgroups of a queue-consuming launch come first (block ids 0 .. cap - 1)
@@ -1610,6 +1635,12 @@ extern "C" int msat_env_launch_threads(const msat_env_desc *desc) {
     EnvParams p;
     if (int rc = make_params(desc, &p)) return rc;
     return env_threads(p);
+}
+
+extern "C" int msat_env_delta_launch_threads(const msat_env_desc *desc) {
+    EnvParams p;
+    if (int rc = make_params(desc, &p)) return rc;
+    return env_delta_threads(p, desc->obs_dtype);
 }
 
 extern "C" int msat_env_group_launch_threads(int32_t total_envs) {

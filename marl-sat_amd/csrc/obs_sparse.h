@@ -98,6 +98,29 @@ MSAT_OS_HD bool sparse_task(const ObsGeom &g, int i, int s, const uint32_t *x, c
     return true;
 }
 
+// The task loop's index: lane `lane` of a T-lane workgroup takes the tasks t = lane, lane + T, lane + 2 T, ... and
+// task t is (agent i, source word s) = (t / U, t % U), U = source words per row.  One division for the first pass;
+// every later pass adds (T / U, T % U) -- task_stride, the same for every lane -- with one conditional carry.
+struct TaskIdx {
+    int i, s;
+};
+MSAT_OS_HD TaskIdx task_first(int lane, int U) {
+    const int i = lane / U;
+    return TaskIdx{i, lane - i * U};
+}
+MSAT_OS_HD TaskIdx task_stride(int T, int U) {
+    const int q = T / U;
+    return TaskIdx{q, T - q * U};
+}
+MSAT_OS_HD void task_advance(TaskIdx &k, const TaskIdx &stride, int U) {
+    k.i += stride.i;
+    k.s += stride.s;
+    if (k.s >= U) {
+        k.s -= U;
+        ++k.i;
+    }
+}
+
 // List entry of the dirty chunk at bit j of k.dirty.  Fast (VEC = 4; bit 31 set): the chunk lies wholly inside the
 // task's live source bits, so its mask and value nibbles come from the task's registers:
 // 1 | chunk index (23 bits) | mask nibble | value nibble.  Slow: the chunk's shifted first index; whoever stores it

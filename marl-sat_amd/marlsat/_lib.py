@@ -117,6 +117,7 @@ def _load():
         "msat_static_var_features": (c_int32, [P, c_int32, c_int32, c_int32, P, P]),
         "msat_reset_queue_words": (c_size_t, [c_int32]),
         "msat_env_launch_threads": (c_int32, [POINTER(EnvDesc)]),
+        "msat_env_delta_launch_threads": (c_int32, [POINTER(EnvDesc)]),
         "msat_env_group_launch_threads": (c_int32, [c_int32]),
         "msat_gae_workspace_bytes": (c_size_t, [c_int32, c_int32]),
         "msat_gae": (
@@ -316,6 +317,7 @@ EXPORTED = (
     "msat_gae",
     "msat_reset_queue_words",
     "msat_env_launch_threads",
+    "msat_env_delta_launch_threads",
     "msat_env_group_launch_threads",
 )
 
