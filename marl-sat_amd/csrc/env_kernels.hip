@@ -162,6 +162,7 @@ struct EnvLds {
                      //        A G = 16 delta step builds no images: fm, fx, fd hold its list of dirty chunks
     uint32_t *sx;    // [WV]   the shadow row's assignment bits
     uint32_t *ssat;  // [WC]   the shadow row's clause-satisfied bits
+    uint16_t *own;   // [V]    agent_of_var (follows red): whose rows a changed element lies in (scatter_obs)
 };
 
 __host__ __device__ __forceinline__ int obs_image_words(const EnvParams &p) { return (p.A * p.D) / 32 + 2; }
@@ -171,10 +172,11 @@ __host__ __device__ __forceinline__ int shadow_row_words(const EnvParams &p) {
     return 1 + ((p.V + 31) >> 5) + ((p.C + 31) >> 5);
 }
 
-// a launch with a shadow (sh) carries the third obs image (fd) and the shadow row's bit words (sx, ssat) as well
+// a launch with a shadow (sh) carries the third obs image (fd), the shadow row's bit words (sx, ssat) and the
+// variables' owners (own: V 16-bit entries) as well
 __host__ __device__ __forceinline__ size_t env_lds_words(const EnvParams &p, bool sh = false) {
     return (size_t)p.WV + p.WC + (size_t)p.A * (p.WC + p.WV) + 2 * (size_t)obs_image_words(p) + 16 +
-           (sh ? (size_t)obs_image_words(p) + 1 + p.WV + p.WC : 0);
+           (sh ? (size_t)obs_image_words(p) + 1 + p.WV + p.WC + (p.V + 1) / 2 : 0);
 }
 
 template <bool SH = false>
@@ -190,6 +192,7 @@ __device__ __forceinline__ EnvLds carve(uint32_t *smem, const EnvParams &p) {
     l.sx = l.fd + (SH ? obs_image_words(p) + 1 : 0);
     l.ssat = l.sx + (SH ? p.WV : 0);
     l.red = reinterpret_cast<int *>(l.ssat + (SH ? p.WC : 0));
+    l.own = reinterpret_cast<uint16_t *>(l.red + 16);
     return l;
 }
 
@@ -461,7 +464,8 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 //   [2] real time at the workgroup's start, [3..6] at four phase ends (3: assignment bits + flips in LDS,
 //   i.e. the first global loads landed; 4: clause scan done; 5: agent tables staged -- the span from 4 holds wave
 //   0's own decision and transition outputs, the write-backs and the staging, no longer a barrier that waits for
-//   lane 0; 6: obs bit images built, or the sparse write's task loop done, its stores issued), [7] at the end, after wave 0's stores
+//   lane 0; a sparse int32 step stages nothing and marks 5 right before its scatter; 6: obs bit images built, or the
+//   sparse write's task loop or scatter done, its stores issued), [7] at the end, after wave 0's stores
 //   have drained (vmcnt(0)).
 // Same CU, same wave: the ratio is the clock that CU ran at while it stepped this env, and the phase times
 // are wave 0's view of the env's dependent chain.
@@ -529,33 +533,19 @@ __device__ __forceinline__ void store_sparse_entry(const EnvParams &p, const Env
 // bytes.  (Until round 10 the tasks listed their chunks in LDS and, behind a barrier, a second pass stored the list one
 // chunk per lane: dense stores on 8 waves, but a prefix sum, an atomic, a barrier and a pass more per env; at 4 waves
 // per workgroup storing in place is the faster form)
-#ifndef MSAT_TASK_CARRY  // 0: A/B builds only (make ab)
-#define MSAT_TASK_CARRY 1
-#endif
+// Since round 11 this is the int8 form alone: int32 observations scatter their changed elements (scatter_obs).
 template <int T, typename ObsT>
 __device__ __forceinline__ void write_obs_sparse16(const EnvParams &p, const EnvLds &l, ObsT *__restrict__ o, int sh,
                                                    const ClockStamp *cs) {
     constexpr int VEC = ObsVec<ObsT>::N;
     const ObsGeom g = obs_geom(p);
     const int U = 2 * ((p.V + 31) >> 5) + ((p.C + 31) >> 5);  // source words per row
-    // int32: (agent, source word) carried from pass to pass (obs_sparse.h): one division per lane instead of one per
-    // lane and pass (five passes of 256 lanes at uf200).  int8 keeps the division: the carried pair cost
+    // one division per lane and pass: the carried (agent, source word) pair of obs_sparse.h cost
     // shadow::env_kernel<2, int8, 256 / 512> a spilled VGPR (8 B of scratch per lane; profiles/r10/resource_usage.txt)
-    constexpr bool kCarry = MSAT_TASK_CARRY && VEC == 4;
-    const TaskIdx stride = task_stride(T, U);
-    TaskIdx ti = task_first((int)threadIdx.x, U);
     for (int t0 = 0; t0 < p.A * U; t0 += T) {
-        int i, s;
-        bool live;
-        if constexpr (kCarry) {
-            i = ti.i, s = ti.s;
-            live = i < p.A;
-            task_advance(ti, stride, U);
-        } else {
-            const int t = t0 + (int)threadIdx.x;
-            i = t / U, s = t - i * U;
-            live = t < p.A * U;
-        }
+        const int t = t0 + (int)threadIdx.x;
+        const int i = t / U, s = t - i * U;
+        const bool live = t < p.A * U;
         SparseTask k;
         uint64_t d = 0;
         if (live && sparse_task<VEC>(g, i, s, l.x, l.sat, l.sx, l.ssat, l.rel, l.nbr, sh, k)) d = k.dirty;
@@ -580,6 +570,81 @@ __device__ __forceinline__ void write_obs_sparse16(const EnvParams &p, const Env
             MSAT_DCHECK((int)o[e] == obs_elem(g, l.x, l.sat, l.rel, l.nbr, e) ? 0 : -1 - e, 1);
     }
 #endif
+}
+
+// Clause c of the scatter below: the lane that evaluated it (pool word w) stores its new status into the rows of the
+// agents it is related to, if the status differs from the shadow row's.  rel[i][c] is "agent i owns a variable of
+// clause c" (agent_tables_kernel), so the rows are the owners of the clause's real literals -- and, for a clause that
+// holds a literal 0, every agent i >= rem when rem > 0 (the reference quirk).  Two literals of
+// one owner store the same value twice.
+__device__ __forceinline__ void scatter_clause(const EnvParams &p, const EnvLds &l, int c, uint64_t w,
+                                               int32_t *__restrict__ o) {
+    const uint32_t ns = l.sat[c >> 5];
+    if ((((ns ^ l.ssat[c >> 5]) >> (c & 31)) & 1u) == 0) return;
+    const int32_t val = (int32_t)((ns >> (c & 31)) & 1u);
+    const int k = p.V + c;
+    bool null_lit = false;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const uint32_t code = (uint32_t)(w >> (16 * j)) & 0xFFFFu;
+        if (code < MSAT_LIT_ABSENT) {
+            const int e = (int)l.own[code >> 1] * p.D + k;
+            MSAT_DCHECK(e, p.A * p.D);
+            o[e] = val;
+        }
+        null_lit |= code == MSAT_LIT_NULL;
+    }
+    if (null_lit && p.rem > 0)  // rare: a plain loop
+        for (int i = p.rem; i < p.A; ++i) o[i * p.D + k] = val;
+}
+
+// The sparse G = 16 delta write of int32 observations: every changed element stored on its own, 4 bytes, by a lane
+// that already holds what decides it -- no agent table in LDS, no barrier behind the clause scan's, no chunks.
+//   clause status   the lane that evaluated clause c in the scan (pool word pw[j], or reloaded past the prefetch);
+//   own variables   lane v: element (own[v], v) if x_v differs from the shadow row's;
+//   neighbours      task t = (agent t / WV, word t % WV): the set bits of (x ^ shadow x) & nbr word, the word from the
+//                   prefetch (pnbr[j] is nbr word tid + j T of the instance) or, past it, from the pool's row.
+// l.own (agent_of_var, 16 bits per variable) was filled before the first barrier of the step.  The bits of l.x, l.sx
+// and the nbr words past V are zero or meet a zero nbr bit.
+template <int T>
+__device__ __forceinline__ void scatter_obs(const EnvParams &p, const EnvLds &l, const msat_pool &pool, int pidx,
+                                            const uint64_t (&pw)[kPfClause], const uint32_t (&pnbr)[kPfNbr],
+                                            int32_t *__restrict__ o) {
+    const int tid = threadIdx.x;
+    const uint64_t *prow = reinterpret_cast<const uint64_t *>(pool.lits) + (size_t)pidx * p.C;
+#pragma unroll
+    for (int j = 0; j < kPfClause; ++j) {
+        const int c = tid + j * T;
+        if (c < p.C) scatter_clause(p, l, c, pw[j], o);
+    }
+    for (int c = tid + kPfClause * T; c < p.C; c += T) scatter_clause(p, l, c, prow[c], o);
+    for (int v = tid; v < p.V; v += T) {
+        const uint32_t xw = l.x[v >> 5];
+        if (((xw ^ l.sx[v >> 5]) >> (v & 31)) & 1u) {
+            const int e = (int)l.own[v] * p.D + v;
+            MSAT_DCHECK(e, p.A * p.D);
+            o[e] = (int32_t)((xw >> (v & 31)) & 1u);
+        }
+    }
+    const uint32_t *nbr_g = pool.nbr + (size_t)pidx * p.A * p.WV;
+    const int ntask = p.A * p.WV;
+    const TaskIdx stride = task_stride(T, p.WV);
+    TaskIdx ti = task_first(tid, p.WV);  // one division per lane; every further pass adds the stride (obs_sparse.h)
+    auto task = [&](uint32_t m) {
+        const uint32_t xw = l.x[ti.s];
+        uint32_t fd = (xw ^ l.sx[ti.s]) & m;
+        const int e0 = ti.i * p.D + p.V + p.C + 32 * ti.s;
+        while (fd) {
+            const int k = __ffs((int)fd) - 1;
+            MSAT_DCHECK(e0 + k, p.A * p.D);
+            o[e0 + k] = (int32_t)((xw >> k) & 1u);
+            fd &= fd - 1;
+        }
+        task_advance(ti, stride, p.WV);
+    };
+#pragma unroll
+    for (int j = 0; j < kPfNbr; ++j) task(pnbr[j]);  // (zero past the table's end)
+    for (int t = tid + kPfNbr * T; t < ntask; t += T) task(nbr_g[t]);
 }
 
 // The prefetch of an instance's pool row and agent tables into this lane's registers (one round trip).
@@ -645,15 +710,16 @@ __device__ __forceinline__ void reset_assignment(const EnvParams &p, const EnvLd
 }
 
 // Stage instance pidx's agent tables in LDS (the first kPf* words from this lane's prefetch registers when pf),
-// build the obs bit images and stream the env's (A, D) block -- or, on a delta step with 16-byte groups, list and
-// store the dirty chunks straight from the source diff (write_obs_sparse16).
+// build the obs bit images and stream the env's (A, D) block -- or, on a delta step with 16-byte groups, store what
+// changed straight from the source diff: int32 observations element by element with nothing staged (scatter_obs),
+// int8 ones the dirty chunks behind the staging (write_obs_sparse16).
 // SH: the launch has an obs shadow (shadow::env_kernel; without one the code is the plain full write).
 template <typename ObsT, int T, bool SH>
 __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const EnvLds &l, const msat_pool &pool,
-                                                    int pidx, bool pf, const uint32_t (&prel)[kPfRel],
-                                                    const uint32_t (&pnbr)[kPfNbr], ObsT *__restrict__ o,
-                                                    const ClockStamp *cs, uint32_t *__restrict__ srow, bool delta,
-                                                    int delta_g, int ndiff) {
+                                                    int pidx, bool pf, const uint64_t (&pw)[kPfClause],
+                                                    const uint32_t (&prel)[kPfRel], const uint32_t (&pnbr)[kPfNbr],
+                                                    ObsT *__restrict__ o, const ClockStamp *cs,
+                                                    uint32_t *__restrict__ srow, bool delta, int delta_g, int ndiff) {
     // srow: the env's obs shadow row (NULL: none), rewritten to describe this write.  delta: l.sx / l.ssat hold the
     // row as it was, it named this instance, and the block holds its image: store only what differs.
     const int tid = threadIdx.x;
@@ -667,6 +733,31 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
     if (SH && srow != nullptr) {
         if (tid == 0) srow[0] = (uint32_t)pidx;
         for (int t = tid; t < nwV + nwC; t += T) srow[1 + t] = t < nwV ? l.x[t] : l.sat[t - nwV];
+    }
+    // int32: a sparse step scatters its changed elements from registers and the bit words (scatter_obs): no table is
+    // staged and no barrier follows the clause scan's (l.x, l.sat, l.sx, l.ssat and l.own are final since then, and
+    // nothing in LDS is written any more).  Marks 3 and 4 bracket the scatter.
+    constexpr bool kScatter = SH && sizeof(ObsT) == 4;
+    if constexpr (kScatter) {
+        if (sparse) {
+            if (cs) cs->mark(3);
+            scatter_obs<T>(p, l, pool, pidx, pw, pnbr, reinterpret_cast<int32_t *>(o));
+            if (cs) cs->mark(4);
+#ifdef MSAT_DEBUG
+            // every element whose value did not change is read back; the evaluator needs the tables in LDS
+            const uint32_t *rel_g = pool.rel + (size_t)pidx * p.A * p.WC;
+            const uint32_t *nbr_g = pool.nbr + (size_t)pidx * p.A * p.WV;
+            for (int t = tid; t < p.A * p.WC; t += T) l.rel[t] = rel_g[t];
+            for (int t = tid; t < p.A * p.WV; t += T) l.nbr[t] = nbr_g[t];
+            lds_barrier();
+            const ObsGeom g = obs_geom(p);
+            for (int e = tid; e < p.A * p.D; e += T) {
+                const int nv = obs_elem(g, l.x, l.sat, l.rel, l.nbr, e);
+                if (nv == obs_elem(g, l.sx, l.ssat, l.rel, l.nbr, e)) MSAT_DCHECK((int)o[e] == nv ? 0 : -1 - e, 1);
+            }
+#endif
+            return;
+        }
     }
     {
         const uint32_t *rel_g = pool.rel + (size_t)pidx * p.A * p.WC;
@@ -690,7 +781,7 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
     }
     lds_barrier();
     if (cs) cs->mark(3);
-    if (SH && sparse) {
+    if (SH && !kScatter && sparse) {  // int8
         write_obs_sparse16<T, ObsT>(p, l, o, (int)((reinterpret_cast<uintptr_t>(o) / sizeof(ObsT)) % ObsVec<ObsT>::N),
                                     cs);
     } else if ((p.ablate & 3) == 0) {
@@ -713,7 +804,8 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
 // Workgroup barriers, by path (every wave of a workgroup takes the same path: each condition below is a function of
 // launch parameters, uniformly loaded words and LDS words that are final since the previous barrier):
 //   running step   B1 assignment bits | B2 flips | B3 clause scan | B5 tables staged | B6 images built (a sparse
-//                  delta step has no B6: its tasks store their chunks themselves)
+//                  delta step has no B6: its tasks store their chunks themselves; with int32 observations it has no
+//                  B5 either: it stages nothing and scatters its changed elements, scatter_obs)
 //   covered        B1 | B2 | B3 | R0 before the reset rewrites l.x | R1 new assignment bits, then the write-back; no obs
 //   in-workgroup   B1 | B2 | B3 | R0 before l.x is rewritten and red[0..1] zeroed | R2 new assignment bits |
 //   reset                        R3 its clause scan | B5 | B6
@@ -795,6 +887,10 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
         // ---- then the loads that do: the instance's pool row and agent tables (second round trip) --------
         prefetch_instance<T>(p, pool, pidx, pw, prel, pnbr);
         __builtin_amdgcn_sched_barrier(0);
+        // a step that may scatter its changed elements (int32, 16-byte groups): the variables' owners, one division
+        // per lane while the prefetch is in flight; read behind the clause scan's barrier
+        if (SH && sizeof(ObsT) == 4 && sa.g == 16 && (MODE == kModeStep || MODE == kModeStepAutoReset))
+            for (int v = tid; v < p.V; v += T) l.own[v] = (uint16_t)agent_of_var(p, v);
         // ---- assignment + the agents' flips (env:230-250) --------------------
         load_x_bits<T>(p, l, xg, x0);
         lds_barrier();
@@ -957,7 +1053,7 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
     // delta: the block holds the image of its shadow row, and that row names this instance (same masks)
     const bool delta = SH && (MODE == kModeStep || MODE == kModeStepAutoReset) && sa.g != 0 && !do_reset &&
                        l.red[5] == pidx;
-    stage_and_write_obs<ObsT, T, SH>(p, l, pool, pidx, (MODE != kModeReset) && !do_reset, prel, pnbr,
+    stage_and_write_obs<ObsT, T, SH>(p, l, pool, pidx, (MODE != kModeReset) && !do_reset, pw, prel, pnbr,
                                      obs + (size_t)b * p.A * p.D, &cs, srow, delta, sa.g, ndiff);
 }
 
@@ -997,7 +1093,7 @@ __device__ __forceinline__ void env_side_reset(const EnvParams &p, const msat_po
     if (tid == 0) st.num_unsat[b] = l.red[0];
     if ((p.ablate & 3) == 2 || obs == nullptr) return;
     // the whole block and a fresh shadow row (its step workgroup touches neither)
-    stage_and_write_obs<ObsT, T, SH>(p, l, pool, pidx, true, prel, pnbr, obs + (size_t)b * p.A * p.D, nullptr,
+    stage_and_write_obs<ObsT, T, SH>(p, l, pool, pidx, true, pw, prel, pnbr, obs + (size_t)b * p.A * p.D, nullptr,
                                      SH ? sa.rows + (size_t)b * shadow_row_words(p) : nullptr, false, 0, 0);
 }
 

@@ -3,7 +3,9 @@
 // diff (x ^ shadow x, sat ^ shadow sat) and the agent tables alone -- no FM / FX / FD bit images.
 //
 // Plain C++ (host and device): the kernel runs these functions on LDS words, tests/obs_sparse_check.cpp runs the
-// same functions on the host against a brute-force get_obs.
+// same functions on the host against a brute-force get_obs.  On the device the chunked tasks (sparse_task,
+// sparse_entry) serve int8 observations; int32 ones scatter their changed elements one by one (scatter_obs in
+// env_kernels.hip), which uses obs_elem (debug read-back) and the carried task index of this file.
 #pragma once
 
 #include <stdint.h>
