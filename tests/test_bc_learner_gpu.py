@@ -43,14 +43,23 @@ def _cfg(H, L, MB, lr=3e-3, **kw):
 _DATA = {}
 
 
-def _dataset(V, C, vpa, n_problems=4, per=2, level=3):
-    """Planted problems, corrupted planted solutions and their oracle labels (host; computed once per shape)."""
+def _dataset(V, C, vpa, n_problems=4, per=2, level=3, pool=None):
+    """Planted problems, corrupted planted solutions and their oracle labels (host; computed once per shape).
+    pool: the name of a pool of tests/irregular_pools.py whose first n_problems instances are the problems (the
+    planted assignments of other instances are then merely the points that get corrupted)."""
     from marlsat.runners.behavioral_cloning import corrupt
     from marlsat.utils.generate_cnf_dataset import generate_sat_clauses, generate_sat_solution, has_isolated_variable
 
-    if (V, C, vpa) in _DATA:
-        return _DATA[(V, C, vpa)]
+    if (V, C, vpa, pool) in _DATA:
+        return _DATA[(V, C, vpa, pool)]
     clauses, sols, seed = [], [], 7000
+    if pool is not None:
+        import irregular_pools
+
+        ir = irregular_pools.get(pool)
+        assert (ir.V, ir.C) == (V, C) and not any(has_isolated_variable(cl[cl != 0], V) for cl in ir.pool)
+        clauses = list(ir.pool[:n_problems])
+        sols = [generate_sat_solution(V, seed + i) for i in range(n_problems)]
     while len(clauses) < n_problems:
         cl = generate_sat_clauses(V, C, seed=seed)
         if not has_isolated_variable(cl, V):
@@ -62,16 +71,16 @@ def _dataset(V, C, vpa, n_problems=4, per=2, level=3):
     pidx = np.repeat(np.arange(n_problems, dtype=np.int32), per)
     ora = OracleSATEnv(V, C, 4, vars_per_agent=vpa)
     labels = np.stack([oracle_labels(ora, clauses[p], x[i].astype(np.int32), 0.0) for i, p in enumerate(pidx)])
-    _DATA[(V, C, vpa)] = (clauses, pidx, x, labels, ora)
-    return _DATA[(V, C, vpa)]
+    _DATA[(V, C, vpa, pool)] = (clauses, pidx, x, labels, ora)
+    return _DATA[(V, C, vpa, pool)]
 
 
-def _learner(V, C, vpa, H, L, MB, n=None, micro_bytes=None, seed=4, lr=3e-3):
+def _learner(V, C, vpa, H, L, MB, n=None, micro_bytes=None, seed=4, lr=3e-3, pool=None):
     from marlsat import SATEnv
     from marlsat.learners.bc_learner import BCLearner
     from marlsat.learners.gnn import GNNActorCritic
 
-    clauses, pidx, x, labels, ora = _dataset(V, C, vpa)
+    clauses, pidx, x, labels, ora = _dataset(V, C, vpa, pool=pool)
     n = len(pidx) if n is None else n
     env = SATEnv(V, C, max_steps=4, vars_per_agent=vpa)
     net = GNNActorCritic(H, L, env.num_agents, env.max_vars_per_agent, 0, V, device="cuda", seed=seed)
@@ -86,8 +95,8 @@ def _unflat(net, flat_params):
     return Pm.to_flax(flat_params.detach().cpu().numpy(), net.H, net.L, net.A, net.M, net.mode, net.E)
 
 
-def _oracle_batch(V, C, vpa, rows):
-    clauses, pidx, x, labels, ora = _dataset(V, C, vpa)
+def _oracle_batch(V, C, vpa, rows, pool=None):
+    clauses, pidx, x, labels, ora = _dataset(V, C, vpa, pool=pool)
     p, xx = pidx[rows], x[rows]
     _, ost = ora.reset(clauses[p], xx.astype(np.int32))
     Ap, An = onet.dense_graph(clauses[p], V)
@@ -124,7 +133,7 @@ def _yard_close(dev, ref, yard, what, extra, failures):
     return worst
 
 
-def _check_trace(learner, net, shape, tag):
+def _check_trace(learner, net, shape, tag, pool=None):
     """Every recorded Adam step against the float64 oracle at the recorded parameters."""
     V, C, vpa, H, L = shape
     trace = learner.trace
@@ -133,7 +142,7 @@ def _check_trace(learner, net, shape, tag):
     failures = []
     for s, rec in enumerate(trace):
         rows = rec["idx"].numpy().astype(np.int64)
-        args, av, am, lab = _oracle_batch(V, C, vpa, rows)
+        args, av, am, lab = _oracle_batch(V, C, vpa, rows, pool=pool)
         P_s = _unflat(net, rec["params"])
         P64 = {k: torch.tensor(a, dtype=torch.float64, requires_grad=True) for k, a in P_s.items()}
         onet.RELU_LOG = log = []
@@ -213,6 +222,26 @@ def test_every_adam_step_matches_oracle(V, C, vpa, H, L, precision_path):
         assert np.array_equal(bits(p0[k]), bits(p1[k])), k
     moved = [k for k in p0 if not np.array_equal(bits(p0[k]), bits(p1[k]))]
     assert {k.split("/")[0].split("_")[0] for k in moved} >= {"encoder", "actor", "agent"}
+
+
+def test_every_adam_step_matches_oracle_on_an_irregular_pool():
+    """The same three Adam steps on the 2-wide pool of tests/irregular_pools.learner_pool: literal 0, [v, v] and
+    [v, -v] rows (the labels are the oracle's greedy ones on those clauses).  The network starts from zero biases,
+    so the pool has no variable outside every clause."""
+    from marlsat import SATEnv
+    from marlsat.runners.behavioral_cloning import compute_joint_labels
+
+    V, C, vpa, H, L = 12, 40, 4, 64, 2
+    clauses, pidx, x, labels, ora = _dataset(V, C, vpa, pool="learner")
+    assert clauses.shape == (4, C, 2) and (clauses[1] == 0).any()
+    env = SATEnv(V, C, max_steps=4, vars_per_agent=vpa)
+    got = compute_joint_labels(env, env.make_pool(clauses), pidx, x, 0.0).cpu().numpy()
+    assert np.array_equal(got, labels) and (labels != env.max_vars_per_agent).any()
+    learner, net, env = _learner(V, C, vpa, H, L, MB=3, n=7, pool="learner")
+    learner.trace = []
+    learner.train_epoch(torch.Generator().manual_seed(7))
+    assert [len(r["idx"]) for r in learner.trace] == [3, 3, 1]
+    _check_trace(learner, net, (V, C, vpa, H, L), "irregular V12 H64", pool="learner")
 
 
 def test_micro_batches_meet_the_same_bars():

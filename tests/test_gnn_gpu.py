@@ -24,14 +24,17 @@ CASES = [  # V, C, vpa, H, L, S, action_mode
 ]
 
 
-def _setup(V, C, vpa, H, L, S, mode, seed=0):
+def _setup(V, C, vpa, H, L, S, mode, seed=0, pool=None, inst=None, x=None):
+    """pool (N, C, K) int32, inst (S,) int32, x (S, V) uint8: the instances and samples to run on (default:
+    generated 3-SAT instances and random samples)."""
     from marlsat.learners.gnn import GNNActorCritic
     from marlsat.learners.graphs import DeviceTemplates, assemble, build_templates
     from marlsat import SATEnv
     from marlsat.utils.generate_cnf_dataset import generate_problem_pool
 
-    N = 4
-    pool = generate_problem_pool(V, C, N, size_id=7)
+    if pool is None:
+        pool = generate_problem_pool(V, C, 4, size_id=7)
+    N = pool.shape[0]
     env = SATEnv(V, C, max_steps=10, vars_per_agent=vpa)
     A, M = env.num_agents, env.max_vars_per_agent
     dpool = env.make_pool(pool)
@@ -41,8 +44,10 @@ def _setup(V, C, vpa, H, L, S, mode, seed=0):
     net.load_flax(tree32)
     tpl = DeviceTemplates(build_templates(pool, V, A), A, "cuda")
     rng = np.random.default_rng(seed)
-    inst = rng.integers(0, N, S).astype(np.int32)
-    x = rng.integers(0, 2, (S, V)).astype(np.uint8)
+    if inst is None:
+        inst = rng.integers(0, N, S).astype(np.int32)
+        x = rng.integers(0, 2, (S, V)).astype(np.uint8)
+    assert inst.shape == (S,) and x.shape == (S, V)
     b = assemble(tpl, dpool.packed, dpool.static_var_features(), torch.from_numpy(inst).cuda(),
                  torch.from_numpy(x).cuda())
     # oracle inputs
@@ -85,6 +90,14 @@ def test_forward_backward_match_oracle(V, C, vpa, H, L, S, mode, fuse, path, mon
     _set_path(monkeypatch, path, c_precision)
     monkeypatch.setattr(GNNActorCritic, "fuse_phi", fuse)
     net, b, P, batch, av, am, A, M = _setup(V, C, vpa, H, L, S, mode)
+    _forward_backward_check(net, b, P, batch, av, am, L, mode, f"small {path} fuse={fuse} V={V} H={H} L={L} mode={mode}")
+
+
+def _forward_backward_check(net, b, P, batch, av, am, L, mode, label):
+    """Logits, value and every parameter gradient (random cotangents) of the device network on batch b against
+    the float64 oracle on `batch`, at the bars of the module docstring.  Returns (report, norm, (logits, value)):
+    report = [(tensor, err / fp32-oracle err)], worst first; norm = the worst err / bound (1.0 = at the bar) of
+    the normwise and of the elementwise bars, over the outputs and over the gradients."""
     args = (batch["svf"], batch["x"], batch["cf"], batch["A_pos"], batch["A_neg"])
     onet.RELU_LOG = log = []
     try:
@@ -94,6 +107,8 @@ def test_forward_backward_match_oracle(V, C, vpa, H, L, S, mode, fuse, path, mon
         onet.RELU_LOG = None
     logits, value, state = net.forward(b, save=True)
     rl, rv = ref_logits.detach().numpy(), ref_value.detach().numpy()
+    norm = {"outputs": max(_norm_ratio(logits.cpu().numpy(), rl, 1e-5), _norm_ratio(value.cpu().numpy(), rv, 1e-5)),
+            "gradients": 0.0}
     _close_norm(logits.cpu().numpy(), rl, 1e-5, "logits")
     _close_norm(value.cpu().numpy(), rv, 1e-5, "value")
     # random cotangents
@@ -107,20 +122,33 @@ def test_forward_backward_match_oracle(V, C, vpa, H, L, S, mode, fuse, path, mon
     obj.backward()
     # the elementwise bar of the depth tests as well: |err| <= 1e-5 |ref| + factor x the fp32 CPU oracle's error
     y_l, y_v, y_g = _fp32_yardstick(P, L, args, av, am, mode, wl, wv)
-    report = []
-    _close_yard(logits.cpu().numpy(), rl, y_l, FWD_FACTOR, "logits", report)
-    _close_yard(value.cpu().numpy(), rv, y_v, FWD_FACTOR, "value", report)
+    report, elem = [], {}
+    _close_yard(logits.cpu().numpy(), rl, y_l, FWD_FACTOR, "logits", report, worst=elem)
+    _close_yard(value.cpu().numpy(), rv, y_v, FWD_FACTOR, "value", report, worst=elem)
+    norm["elementwise outputs"] = max(elem.values())
     net.grads.zero_()
     net.backward(b, state, wl.float().cuda().contiguous(), wv.float().cuda().contiguous())
     got = net.to_flax(grads=True)
     for name, p in P.items():
         ref = p.grad.numpy() if p.grad is not None else np.zeros(p.shape)
         scale = max(np.abs(ref).max(), 1e-12)
+        norm["gradients"] = max(norm["gradients"], _norm_ratio(got[name], ref, 1e-4))
         _close(got[name], ref, 0.0, 1e-4 * scale, f"grad {name}")
-        _close_yard(got[name], ref, y_g[name], GRAD_FACTOR, f"grad {name}", report, kink[name])
+        _close_yard(got[name], ref, y_g[name], GRAD_FACTOR, f"grad {name}", report, kink[name], worst=elem)
+    norm["elementwise gradients"] = max(v for k, v in elem.items() if k.startswith("grad"))
     report.sort(key=lambda t: -t[1])
-    print(f"small {path} fuse={fuse} V={V} H={H} L={L} mode={mode}: err / fp32-oracle err, worst",
-          [(w, round(r, 2)) for w, r in report[:4]])
+    print(f"{label}: err / fp32-oracle err, worst", [(w, round(r, 2)) for w, r in report[:4]],
+          "worst err / bound", {k: round(v, 3) for k, v in norm.items()})
+    return report, norm, (logits, value)
+
+
+def _norm_ratio(dev, ref, rtol):
+    """max |dev - ref| over (rtol x max |ref|) on the finite elements of ref: 1.0 = at the normwise bar."""
+    dev, ref = np.asarray(dev, np.float64), np.asarray(ref, np.float64)
+    fin = np.isfinite(ref) & np.isfinite(dev)
+    if not fin.any():
+        return 0.0
+    return float(np.abs(dev[fin] - ref[fin]).max() / (rtol * max(np.abs(ref[fin]).max(), 1e-12)))
 
 
 DEPTH_CASES = [  # the reference's depth (MAPPO_CONFIG.yaml:23-24: H = 128, L = 16)
@@ -151,9 +179,10 @@ def _fp32_yardstick(P, L, args, av, am, mode, wl, wv):
     return lg.detach().numpy(), v.detach().numpy(), grads
 
 
-def _close_yard(dev, ref, yard, factor, what, report, kink=None):
+def _close_yard(dev, ref, yard, factor, what, report, kink=None, worst=None):
     """|dev - ref| <= 1e-5 |ref| + factor * max|yard - ref| (+ kink) elementwise (yard: the fp32 CPU
-    oracle; kink: oracle.net.kink_bound's allowance for ReLU inputs within fp32 noise of 0)."""
+    oracle; kink: oracle.net.kink_bound's allowance for ReLU inputs within fp32 noise of 0).  worst: a dict that
+    receives, under `what`, the largest err / bound over the elements (1.0 = at the bar)."""
     dev, ref, yard = (np.asarray(a, np.float64) for a in (dev, ref, yard))
     fin = np.isfinite(ref)
     assert np.array_equal(fin, np.isfinite(dev)), what + " (inf pattern)"
@@ -163,6 +192,8 @@ def _close_yard(dev, ref, yard, factor, what, report, kink=None):
     plain = extra[fin] == 0  # the ratio is reported over the elements without a ReLU-kink allowance
     report.append((what, float(err[plain].max() / max(e32, 1e-300)) if plain.any() else 0.0))
     bound = 1e-5 * np.abs(ref[fin]) + factor * e32 + extra[fin]
+    if worst is not None:
+        worst[what] = float((err / np.maximum(bound, 1e-300)).max()) if err.size else 0.0
     assert (err <= bound).all(), f"{what}: max err {err.max():.3g}, worst ratio {(err / bound).max():.3g}"
 
 
@@ -276,21 +307,32 @@ def test_critic_only_batch_matches_full():
     assert torch.equal(v_full, v_crit)
 
 
-@pytest.mark.parametrize("mode,padded", [(0, False), (1, False), (0, True)], ids=["0", "1", "0-padded"])
-def test_ppo_loss_and_grads_match_oracle(mode, padded):
+@pytest.mark.parametrize("mode,padded,pool", [(0, False, None), (1, False, None), (0, True, None),
+                                              (0, True, "quirks23"), (1, True, "quirks23")],
+                         ids=["0", "1", "0-padded", "0-quirks23", "1-quirks23"])
+def test_ppo_loss_and_grads_match_oracle(mode, padded, pool):
+    """pool: a pool of tests/irregular_pools.py in place of the generated instances (quirks23: literal 0, repeated
+    variables, a variable in no clause, an agent whose graph has no clause row; agents of 8, 8 and 7)."""
     from marlsat import _lib
 
     V, C, vpa, H, L, S = (20, 91, 10, 64, 2, 6) if mode == 0 else (16, 60, 4, 64, 2, 6)
     if padded:  # agents of 8, 8 and 7 variables: masked lanes in the loss, a -inf logit column, zeroed my_emb slots
         V, C = 23, 97
-    net, b, P, batch, av, am, A, M = _setup(V, C, vpa, H, L, S, mode, seed=5)
+    kw = {}
+    if pool is not None:
+        import irregular_pools
+
+        ir = irregular_pools.get(pool)
+        V, C, vpa, S = ir.V, ir.C, ir.vpa, len(ir.inst)
+        kw = dict(pool=ir.pool, inst=ir.inst, x=ir.x)
+    net, b, P, batch, av, am, A, M = _setup(V, C, vpa, H, L, S, mode, seed=5, **kw)
     assert padded == (not bool(am.all()))
     cfg = {"CLIP_EPS": 0.12, "VF_CLIP": 0.5, "ENT_COEF": 0.005, "VF_COEF": 0.5}
     rng = np.random.default_rng(9)
     with torch.no_grad():
         lg = onet.actor_logits(P, L, batch["svf"], batch["x"], batch["cf"], batch["A_pos"], batch["A_neg"], av, am, mode)
         vv = onet.critic(P, L, batch["svf"], batch["x"], batch["cf"], batch["A_pos"], batch["A_neg"])
-        probs = torch.softmax(lg, -1)
+        probs = torch.softmax(onet._live_rows(lg), -1)  # a padded mode-1 slot (both logits -inf) draws either action
         act = torch.distributions.Categorical(probs=probs).sample(generator=None) if False else \
             torch.multinomial(probs.reshape(-1, probs.shape[-1]), 1, generator=torch.Generator().manual_seed(1)) \
             .reshape(probs.shape[:-1])
@@ -383,9 +425,13 @@ def test_fused_encoder_matches_reference_order_uf50():
 def test_gathers_and_degree_features():
     """msat_clause_gather2 (split / merged) and msat_var_gather2 with distinct pos / neg sources
     against dense incidence products, and the assembled count features (vfeat[:, 4:6], cdeg)."""
+    net, b, P, batch, av, am, A, M = _setup(20, 91, 10, 64, 2, 5, 0)
+    _check_gathers(b)
+
+
+def _check_gathers(b):
     from marlsat import _lib
 
-    net, b, P, batch, av, am, A, M = _setup(20, 91, 10, 64, 2, 5, 0)
     H, Nv, Nc = 64, b.Nv, b.Nc
     slots = b.slots.cpu().numpy()
     Ap = np.zeros((Nv, Nc))

@@ -24,8 +24,14 @@ def _cfg(**kw):
     return c
 
 
-@pytest.mark.parametrize("mode", [0, 1])
-def test_train_cycle_matches_oracle_replay(mode):
+@pytest.mark.parametrize("mode,irregular", [(0, False), (1, False), (0, True), (1, True)],
+                         ids=["0", "1", "0-irregular", "1-irregular"])
+def test_train_cycle_matches_oracle_replay(mode, irregular):
+    """irregular: the 2-wide pool of tests/irregular_pools.learner_pool (literal 0, [v, v] and [v, -v] rows) in place
+    of the generated 3-SAT one.  The env takes a literal 0 as the last variable's agent's (its obs quirk) while
+    the network's adjacency ignores it, so the rollout's stored log-probs, values, GAE and every Adam step are
+    checked where the two differ.  The network starts from the flax zero biases here: a variable in no clause
+    would be a constant row through every LayerNorm, so that pool has none."""
     from marlsat import SATEnv
     from marlsat.learners.gnn import GNNActorCritic
     from marlsat.learners.mappo_gnn_sat_learner import MAPPOLearner, learning_rate_at
@@ -35,6 +41,12 @@ def test_train_cycle_matches_oracle_replay(mode):
     V, C, vpa = (12, 40, 4) if mode == 0 else (12, 40, 3)
     cfg = _cfg(action_mode=mode)
     pool = generate_problem_pool(V, C, 6, size_id=11)
+    if irregular:
+        import irregular_pools
+
+        ir = irregular_pools.get("learner")
+        assert (ir.V, ir.C, ir.pool.shape) == (V, C, (6, C, 2)) and (ir.pool == 0).any()
+        pool = ir.pool
     env = SATEnv(V, C, max_steps=3, vars_per_agent=vpa, action_mode=mode)
     A, M = env.num_agents, env.max_vars_per_agent
     net = GNNActorCritic(64, 2, A, M, mode, V, device="cuda", seed=3)
@@ -105,7 +117,7 @@ def test_train_cycle_matches_oracle_replay(mode):
     got = np.stack([metrics["epoch_value_losses"].reshape(-1), metrics["epoch_actor_losses"].reshape(-1),
                     metrics["epoch_entropies"].reshape(-1)], 1)
     lerr = np.abs(got - np.array(losses)) / (np.abs(np.array(losses)) + 1e-5)
-    print(f"replay mode {mode}: loss error / (|loss| + 1e-5) max {lerr.max():.3g}")
+    print(f"replay mode {mode} irregular {irregular}: loss error / (|loss| + 1e-5) max {lerr.max():.3g}")
     # measured on MI355X (profiles/r04i_parity.log): loss error <= 2.0e-5 relative, update norm <= 2.5e-4
     np.testing.assert_allclose(got, np.array(losses), rtol=5e-5, atol=1e-5)
     # Adam divides by sqrt(v), so an element whose gradient is near fp32 noise at some step moves by a
@@ -121,7 +133,7 @@ def test_train_cycle_matches_oracle_replay(mode):
         ratios.append(diff / max(upd, 1e-30))
         assert diff <= 1e-3 * upd + 1e-7, (kk, diff, upd)
         assert np.abs(final[kk] - ref).max() <= 2.0 * lr_sum + 1e-6, kk
-    print(f"replay mode {mode}: |update - oracle update| / |oracle update| worst {max(ratios):.3g}, median "
+    print(f"replay mode {mode} irregular {irregular}: |update - oracle update| / |oracle update| worst {max(ratios):.3g}, median "
           f"{float(np.median(ratios)):.3g}")
     # cycle metrics (learner:661-719) from the recorded transitions + the oracle critic on the final params
     done = tr["done"].astype(bool)
