@@ -223,6 +223,16 @@ constexpr int kPfClause = 4;
 constexpr int kPfRel = 4;
 constexpr int kPfNbr = 2;
 
+// Every global load this wave has issued has landed behind this point, and the compiler's wait-count bookkeeping knows
+// it (an s_waitcnt in inline asm is opaque to it).  gfx950 counts loads and stores in the one vmcnt, so a register
+// the bookkeeping believes some load under an earlier branch may still be writing (the cold tail loops of the
+// actions, the shadow row and the assignment bytes, the reset-queue rank scan: a wait on one branch does not clear
+// the state on the path that skipped it) gets a vmcnt(0) at its next definition -- and behind the clause scan's first
+// byte stores that wait is a store round trip, once per slice and once per scattered store (DESIGN.md section 4,
+// round 12).  The gfx9 encoding: vmcnt = imm[15:14]:imm[3:0] = 0; expcnt imm[6:4] and lgkmcnt imm[11:8] at their
+// maxima (not waited for).
+__device__ __forceinline__ void retire_loads() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
 // One 64-clause wave slice of the clause scan: c0 wave-uniform, w = this lane's pool word.
 template <bool kPbrs>
 __device__ __forceinline__ void clause_slice(const EnvParams &p, const EnvLds &l, int c0, uint64_t w,
@@ -268,6 +278,7 @@ __device__ __forceinline__ void eval_clauses(const EnvParams &p, const EnvLds &l
     for (int c0 = (threadIdx.x & ~63) + NPF * T; c0 < cend; c0 += T) {
         const int c = c0 + lane;
         const uint64_t w = c < p.C ? prow[c] : 0ull;  // pool rows are shared by many envs: keep them cached
+        retire_loads();
         clause_slice<kPbrs>(p, l, c0, w, sat_g, ntrue_g, unsat, newly);
     }
     if (lane == 0) {
@@ -617,7 +628,11 @@ __device__ __forceinline__ void scatter_obs(const EnvParams &p, const EnvLds &l,
         const int c = tid + j * T;
         if (c < p.C) scatter_clause(p, l, c, pw[j], o);
     }
-    for (int c = tid + kPfClause * T; c < p.C; c += T) scatter_clause(p, l, c, prow[c], o);
+    for (int c = tid + kPfClause * T; c < p.C; c += T) {
+        const uint64_t w = prow[c];
+        retire_loads();
+        scatter_clause(p, l, c, w, o);
+    }
     for (int v = tid; v < p.V; v += T) {
         const uint32_t xw = l.x[v >> 5];
         if (((xw ^ l.sx[v >> 5]) >> (v & 31)) & 1u) {
@@ -644,7 +659,11 @@ __device__ __forceinline__ void scatter_obs(const EnvParams &p, const EnvLds &l,
     };
 #pragma unroll
     for (int j = 0; j < kPfNbr; ++j) task(pnbr[j]);  // (zero past the table's end)
-    for (int t = tid + kPfNbr * T; t < ntask; t += T) task(nbr_g[t]);
+    for (int t = tid + kPfNbr * T; t < ntask; t += T) {
+        const uint32_t m = nbr_g[t];
+        retire_loads();
+        task(m);
+    }
 }
 
 // The prefetch of an instance's pool row and agent tables into this lane's registers (one round trip).
@@ -946,6 +965,12 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
             }
         }
         lds_barrier();
+        // every load of the step so far -- the first round trip, the prefetch (issued two phases ago; the scan needs its
+        // pool words here anyway), the cold tail loops -- is retired at this one point, which dominates the scan, the
+        // decision, the write-backs and the scatter: behind it no register carries a pending load, so none of them
+        // waits for the wave's own stores.  In the kernels with an obs shadow only: the launches without one stage the
+        // rel / nbr prefetch behind the scan and measured 0.3-0.7 % slower with the wait here
+        if (SH) retire_loads();
         // ---- clause scan of the stepped assignment (env:252-254); a covered env (a reset workgroup of this launch
         // resets it: it times out now, listed by the previous launch) leaves its clause state to that workgroup
         covered = rq_fast && l.red[3] != 0;
