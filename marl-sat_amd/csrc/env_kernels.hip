@@ -23,34 +23,18 @@
 //   reset + masks           :158-181, :99-128
 //   get_obs                 :345-398
 //   rollout auto-reset      src/learners/mappo_gnn_sat_learner.py:422-464
+//
+// This file holds the step / reset / obs kernel family, its launchers and its entry points, and nothing else: the
+// cold kernels around the env live in env_tables.hip and bc_data.hip and share env_params.h with it.
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
-#include "common.h"
+#include "env_params.h"
 #include "obs_sparse.h"
 
 namespace msat {
-
-constexpr int kThreads = 256;
-
-struct EnvParams {
-    int B, V, C, K, A, M, D;
-    int WV, WC;     // uint32 words per agent row of the nbr / rel tables (even: whole 64-bit ballots)
-    int base, rem;  // agent i owns [i*base + min(i,rem), +base+(i<rem))
-    int max_steps, action_mode, reward_mode, N;
-    float r_clause, r_sat, gamma;
-    int ablate;  // diagnostics only (MARLSAT_ABLATE): bits 0-1: 0 full, 1 constant obs, 2 no obs write;
-                 // bit 2: disable the XCD-major env order
-    // debug builds (MSAT_DCHECK): elements from each caller buffer's pointer to the end of its allocation
-    // (dbg_extent); 0 in product builds
-    long long dbg_obs, dbg_assign, dbg_sat, dbg_ntrue, dbg_actions;
-    // reset queue (msat_env_state.reset_queue): 0 none; 1 this autoreset launch consumes the list the previous
-    // one made and makes the next one's (launch B + rq_cap workgroups); 2 the launch clears the entries of the
-    // envs it modifies (the other state-modifying calls)
-    int rq_mode, rq_cap;
-    uint32_t rq_serial;
-};
 
 // Obs shadow (msat_env_step_delta), an argument of shadow::env_kernel alone: per env, what the obs buffer holds --
 // [problem_idx or -1 | x bit words | clause-sat bit words] (shadow_row_words).  With it a step stores only the obs
@@ -139,15 +123,6 @@ __device__ __forceinline__ int rq_scan(const uint32_t *__restrict__ pend, int B,
     return total_below;
 }
 
-__host__ __device__ __forceinline__ int agent_lo(const EnvParams &p, int i) { return i * p.base + (i < p.rem ? i : p.rem); }
-__host__ __device__ __forceinline__ int agent_size(const EnvParams &p, int i) { return p.base + (i < p.rem ? 1 : 0); }
-
-__device__ __forceinline__ int agent_of_var(const EnvParams &p, int v) {
-    const int split = p.rem * (p.base + 1);
-    if (v < split) return v / (p.base + 1);
-    return p.rem + (v - split) / p.base;  // base > 0 whenever v >= split
-}
-
 // LDS image of one environment (all uint32 words).
 struct EnvLds {
     uint32_t *x;    // [WV]    assignment bits
@@ -159,7 +134,7 @@ struct EnvLds {
     int *red;       // [16]    reduction / broadcast scratch
     // only in a launch with an obs shadow (carve<true>):
     uint32_t *fd;    // [NW+1] obs image: element differs from what the obs buffer holds (follows fx; G = 64 / 128).
-                     //        A G = 16 delta step builds no images: fm, fx, fd hold its list of dirty chunks
+                     //        A G = 16 delta step builds no images and leaves fm, fx, fd alone
     uint32_t *sx;    // [WV]   the shadow row's assignment bits
     uint32_t *ssat;  // [WC]   the shadow row's clause-satisfied bits
     uint16_t *own;   // [V]    agent_of_var (follows red): whose rows a changed element lies in (scatter_obs)
@@ -195,8 +170,6 @@ __device__ __forceinline__ EnvLds carve(uint32_t *smem, const EnvParams &p) {
     l.own = reinterpret_cast<uint16_t *>(l.red + 16);
     return l;
 }
-
-__device__ __forceinline__ uint32_t bit(const uint32_t *w, int i) { return (w[i >> 5] >> (i & 31)) & 1u; }
 
 // Assignment bytes -> LDS bit words, one ballot per 64 vars.  x0: this lane's byte of the first pass
 // (var threadIdx.x, loaded early by the caller; any value where threadIdx.x >= V).
@@ -461,12 +434,11 @@ __device__ __forceinline__ int xcd_major(int blk, int n, bool off) {
     return (!off && (n & 7) == 0) ? (blk & 7) * (n >> 3) + (blk >> 3) : blk;
 }
 
-// Workgroup barrier for LDS only: waits for this wave's LDS operations, not for its global stores
-// (a __syncthreads() fence drains every outstanding store).  env_run never reads back global memory
-// written by another thread of its workgroup.  (A persistent variant that walks several envs per
+// Every workgroup barrier below is barrier_lds() (common.h), for LDS only: it waits for this wave's LDS operations,
+// not for its global stores (a __syncthreads() fence drains every outstanding store).  env_run never reads back
+// global memory written by another thread of its workgroup.  (A persistent variant that walks several envs per
 // workgroup to overlap one env's store drain with the next env's scan measured slower at every
 // occupancy, 114-188 us vs 112 us at uf200 x 4096: the 8 resident workgroups per CU already overlap.)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Diagnostic stamps (msat_step_out.clock_stamps, NULL in product calls: a wave-uniform branch at each
 // point).  Per env, 8 words written by lane 0 of wave 0 (vector stores):
@@ -768,7 +740,7 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
             const uint32_t *nbr_g = pool.nbr + (size_t)pidx * p.A * p.WV;
             for (int t = tid; t < p.A * p.WC; t += T) l.rel[t] = rel_g[t];
             for (int t = tid; t < p.A * p.WV; t += T) l.nbr[t] = nbr_g[t];
-            lds_barrier();
+            barrier_lds();
             const ObsGeom g = obs_geom(p);
             for (int e = tid; e < p.A * p.D; e += T) {
                 const int nv = obs_elem(g, l.x, l.sat, l.rel, l.nbr, e);
@@ -798,14 +770,14 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
             for (int t = tid; t < (SH && delta ? 3 * obs_image_words(p) + 1 : 2 * obs_image_words(p)); t += T)
                 l.fm[t] = 0u;  // fm, fx, fd contiguous
     }
-    lds_barrier();
+    barrier_lds();
     if (cs) cs->mark(3);
     if (SH && !kScatter && sparse) {  // int8
         write_obs_sparse16<T, ObsT>(p, l, o, (int)((reinterpret_cast<uintptr_t>(o) / sizeof(ObsT)) % ObsVec<ObsT>::N),
                                     cs);
     } else if ((p.ablate & 3) == 0) {
         build_obs_images<T, SH>(p, l, delta);
-        lds_barrier();
+        barrier_lds();
         if (cs) cs->mark(4);
         if (SH && delta)
             write_obs_delta<T, ObsT>(p, l, o, delta_g);
@@ -912,7 +884,7 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
             for (int v = tid; v < p.V; v += T) l.own[v] = (uint16_t)agent_of_var(p, v);
         // ---- assignment + the agents' flips (env:230-250) --------------------
         load_x_bits<T>(p, l, xg, x0);
-        lds_barrier();
+        barrier_lds();
         cs.mark(1);
         if (SH) {  // the shadow row -> red[5] (the instance it names), l.sx, l.ssat
             const int nwV = (p.V + 31) >> 5;
@@ -964,7 +936,7 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
                 }
             }
         }
-        lds_barrier();
+        barrier_lds();
         // every load of the step so far -- the first round trip, the prefetch (issued two phases ago; the scan needs its
         // pool words here anyway), the cold tail loops -- is retired at this one point, which dominates the scan, the
         // decision, the write-backs and the scatter: behind it no register carries a pending load, so none of them
@@ -980,7 +952,7 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
             eval_clauses<T, true, kPfClause>(p, l, pool.lits, pidx, scan_sat, scan_ntrue, pw);
         else
             eval_clauses<T, false, kPfClause>(p, l, pool.lits, pidx, scan_sat, scan_ntrue, pw);
-        lds_barrier();
+        barrier_lds();
         cs.mark(2);
         // ---- the decision, taken by every wave for itself from what the scan's barrier published (red[0], red[3])
         // and the uniformly loaded step0: nothing is broadcast, nobody waits for lane 0's transition outputs
@@ -1044,14 +1016,14 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
         // the reset rewrites l.x and zeroes red[0..1], so it waits for them first.  Uniform: do_reset is a function of
         // red[0], red[3] (both final since the scan's barrier, neither written before this one), step0 and the
         // launch's parameters, the same values in every wave.
-        if (MODE != kModeReset) lds_barrier();
+        if (MODE != kModeReset) barrier_lds();
         pidx = reset_instance(p, new_pidx, seed, ctr, b);
         if (MSAT_DEBUG_BUILD && tid == 0) MSAT_DCHECK(pidx, p.N);  // the reset's pool row
         reset_assignment<T>(p, l, new_assign, seed, ctr, b);
         if (covered) {
             // the reset workgroup scans the new instance and writes its clause state, count and observation;
             // this one writes the fields it read: assignment, step, done, problem_idx
-            lds_barrier();
+            barrier_lds();
             if (tid == 0) {
                 st.step[b] = 0;
                 st.done[b] = 0;
@@ -1061,9 +1033,9 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
             return;
         }
         if (tid < 2) l.red[tid] = 0;  // (every wave has read them: the barrier above)
-        lds_barrier();
+        barrier_lds();
         eval_clauses<T, false, 0>(p, l, pool.lits, pidx, sat_g, ntrue_g, pw);
-        lds_barrier();
+        barrier_lds();
         if (tid == 0) {
             st.num_unsat[b] = l.red[0];
             st.step[b] = 0;
@@ -1101,7 +1073,7 @@ __device__ __forceinline__ void env_side_reset(const EnvParams &p, const msat_po
         if (tid == 0) l.red[4] = b;
     }
     if (tid < 4) l.red[tid] = 0;
-    lds_barrier();
+    barrier_lds();
     const int b = l.red[4];
     if (b < 0) return;  // fewer than j + 1 envs time out in this launch
     const int pidx = reset_instance(p, new_pidx, seed, ctr, b);
@@ -1110,11 +1082,11 @@ __device__ __forceinline__ void env_side_reset(const EnvParams &p, const msat_po
     uint32_t prel[kPfRel], pnbr[kPfNbr];
     prefetch_instance<T>(p, pool, pidx, pw, prel, pnbr);
     reset_assignment<T>(p, l, new_assign, seed, ctr, b);
-    lds_barrier();
+    barrier_lds();
     uint8_t *__restrict__ sat_g = st.clause_sat + (size_t)b * p.C;
     uint8_t *__restrict__ ntrue_g = st.clause_ntrue ? st.clause_ntrue + (size_t)b * p.C : nullptr;
     eval_clauses<T, false, kPfClause>(p, l, pool.lits, pidx, sat_g, ntrue_g, pw);
-    lds_barrier();
+    barrier_lds();
     if (tid == 0) st.num_unsat[b] = l.red[0];
     if ((p.ablate & 3) == 2 || obs == nullptr) return;
     // the whole block and a fresh shadow row (its step workgroup touches neither)
@@ -1223,300 +1195,13 @@ env_group_kernel(EnvGroups gs, uint64_t seed, uint64_t ctr) {
     cs.finish();
 }
 
-// ---------------------------------------------------------------- cold path --
-
-__global__ void pool_pack_kernel(const int32_t *__restrict__ lits, int NC, int K, int V,
-                                 uint16_t *__restrict__ pool, int32_t *__restrict__ err) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= NC) return;
-    uint64_t w = 0;
-#pragma unroll
-    for (int j = 0; j < MSAT_LIT_SLOTS; ++j) {
-        uint32_t code = MSAT_LIT_ABSENT;
-        if (j < K) {
-            const int lit = lits[(size_t)t * K + j];
-            if (lit == 0) {
-                code = MSAT_LIT_NULL;
-            } else {
-                const int a = lit < 0 ? -lit : lit;
-                if (a > V) {
-                    atomicOr(err, 1);
-                    code = MSAT_LIT_NULL;
-                } else {
-                    code = ((uint32_t)(a - 1) << 1) | (lit < 0 ? 1u : 0u);
-                }
-            }
-        }
-        w |= (uint64_t)code << (16 * j);
-    }
-    reinterpret_cast<uint64_t *>(pool)[t] = w;
-}
-
-// Per-instance agent tables (env:99-128): rel[i][c] = clause c contains a var of
-// agent i; nbr[i][v] = v appears in a clause related to i and is not i's.
-__global__ void __launch_bounds__(kThreads)
-agent_tables_kernel(EnvParams p, const uint16_t *__restrict__ lits, uint32_t *__restrict__ rel_g,
-                    uint32_t *__restrict__ nbr_g) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    uint32_t *rel = smem;
-    uint32_t *nbr = rel + (size_t)p.A * p.WC;
-    const int n = blockIdx.x;
-    for (int t = threadIdx.x; t < p.A * (p.WC + p.WV); t += kThreads) smem[t] = 0u;
-    __syncthreads();
-    const uint64_t *prow = reinterpret_cast<const uint64_t *>(lits) + (size_t)n * p.C;
-    for (int c = threadIdx.x; c < p.C; c += kThreads) {
-        const uint64_t w = prow[c];
-        int vars[3], ags[3];
-        bool nullLit = false;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const uint32_t lit = (uint32_t)(w >> (16 * j)) & 0xFFFFu;
-            vars[j] = lit < MSAT_LIT_ABSENT ? (int)(lit >> 1) : -1;
-            ags[j] = vars[j] >= 0 ? agent_of_var(p, vars[j]) : -1;
-            nullLit |= (lit == MSAT_LIT_NULL);
-        }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            if (ags[j] < 0) continue;
-            atomicOr(&rel[ags[j] * p.WC + (c >> 5)], 1u << (c & 31));
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                if (k == j || vars[k] < 0 || ags[k] == ags[j]) continue;
-                atomicOr(&nbr[ags[j] * p.WV + (vars[k] >> 5)], 1u << (vars[k] & 31));
-            }
-        }
-        if (nullLit && p.rem > 0) {
-            // Reference quirk: literal 0 decodes to var index -1, equal to the -1 padding of
-            // agent_vars rows, so the clause is "related" to every agent owning fewer than M vars.
-            for (int i = p.rem; i < p.A; ++i) {
-                atomicOr(&rel[i * p.WC + (c >> 5)], 1u << (c & 31));
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    if (vars[k] < 0 || ags[k] == i) continue;
-                    atomicOr(&nbr[i * p.WV + (vars[k] >> 5)], 1u << (vars[k] & 31));
-                }
-            }
-        }
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < p.A * p.WC; t += kThreads) rel_g[(size_t)n * p.A * p.WC + t] = rel[t];
-    for (int t = threadIdx.x; t < p.A * p.WV; t += kThreads) nbr_g[(size_t)n * p.A * p.WV + t] = nbr[t];
-}
-
-// Per-env materialisation of the reference's mask tensors (env:99-128, :160).
-__global__ void __launch_bounds__(kThreads)
-env_masks_kernel(EnvParams p, msat_pool pool, const int32_t *__restrict__ problem_idx, int32_t *__restrict__ acm,
-                 int32_t *__restrict__ anm, int32_t *__restrict__ l2a) {
-    const int b = blockIdx.x;
-    const int pidx = problem_idx[b];
-    const uint32_t *rel = pool.rel + (size_t)pidx * p.A * p.WC;
-    const uint32_t *nbr = pool.nbr + (size_t)pidx * p.A * p.WV;
-    if (acm)
-        for (int t = threadIdx.x; t < p.A * p.C; t += kThreads) {
-            const int i = t / p.C, c = t - i * p.C;
-            acm[(size_t)b * p.A * p.C + t] = bit(rel + i * p.WC, c) ? 1 : -1;
-        }
-    if (anm)
-        for (int t = threadIdx.x; t < p.A * p.V; t += kThreads) {
-            const int i = t / p.V, v = t - i * p.V;
-            anm[(size_t)b * p.A * p.V + t] = bit(nbr + i * p.WV, v) ? 1 : -1;
-        }
-    if (l2a) {
-        const uint64_t *prow = reinterpret_cast<const uint64_t *>(pool.lits) + (size_t)pidx * p.C;
-        const int last_agent = agent_of_var(p, p.V - 1);  // var2agent[-1] wraps to the last var
-        for (int t = threadIdx.x; t < p.C * p.K; t += kThreads) {
-            const int c = t / p.K, j = t - c * p.K;
-            const uint32_t lit = (uint32_t)(prow[c] >> (16 * j)) & 0xFFFFu;
-            l2a[(size_t)b * p.C * p.K + t] = lit == MSAT_LIT_NULL ? last_agent : agent_of_var(p, (int)(lit >> 1));
-        }
-    }
-}
-
-__global__ void clause_features_kernel(int BC, const uint8_t *__restrict__ sat,
-                                       const uint8_t *__restrict__ ntrue, float *__restrict__ f) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= BC) return;
-    f[3 * (size_t)t + 0] = (float)sat[t];
-    f[3 * (size_t)t + 1] = (float)ntrue[t] / 3.0f;
-    f[3 * (size_t)t + 2] = 1.0f;
-}
-
-__global__ void __launch_bounds__(kThreads)
-static_var_features_kernel(const uint16_t *__restrict__ pool, int V, int C, float *__restrict__ f) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    int *deg = reinterpret_cast<int *>(smem);  // [2V]
-    const int n = blockIdx.x;
-    for (int t = threadIdx.x; t < 2 * V; t += kThreads) deg[t] = 0;
-    __syncthreads();
-    const uint64_t *prow = reinterpret_cast<const uint64_t *>(pool) + (size_t)n * C;
-    for (int c = threadIdx.x; c < C; c += kThreads) {
-        const uint64_t w = prow[c];
-        for (int j = 0; j < 3; ++j) {
-            const uint32_t lit = (uint32_t)(w >> (16 * j)) & 0xFFFFu;
-            if (lit < MSAT_LIT_ABSENT) atomicAdd(&deg[2 * (lit >> 1) + (lit & 1)], 1);
-        }
-    }
-    __syncthreads();
-    for (int v = threadIdx.x; v < V; v += kThreads) {
-        float *o = f + ((size_t)n * V + v) * 3;
-        o[0] = (float)deg[2 * v] / (float)C;
-        o[1] = (float)deg[2 * v + 1] / (float)C;
-        o[2] = 0.0f;
-    }
-}
-
-// ------------------------------------------------------- BC joint labels ----
-// behavioral_cloning.py:54-100 (compute_joint_labels_parallel_greedy) for a batch: per env,
-// delta[v] = unsat(x with v flipped) - unsat(x) for every var (one pass over the clauses: a clause
-// changes status under the flip of v iff re-evaluating it with v flipped differs; duplicate vars in
-// a clause are counted once, literal 0 stays false), then per agent the first local index with the
-// smallest delta among strictly improving flips; label = that index if best < tau, else M (no-op).
-__global__ void __launch_bounds__(kThreads)
-bc_labels_kernel(EnvParams p, const uint16_t *__restrict__ lits, const int32_t *__restrict__ pidx,
-                 const uint8_t *__restrict__ assign, float tau, int32_t *__restrict__ labels,
-                 int32_t *__restrict__ deltas) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    uint32_t *xb = smem;                               // [WV] assignment bits
-    int *dl = reinterpret_cast<int *>(smem + p.WV);    // [V]
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const uint8_t *xg = assign + (size_t)b * p.V;
-    for (int t = tid; t < p.WV; t += kThreads) {
-        uint32_t w = 0;
-        for (int k = 0; k < 32; ++k) {
-            const int v = 32 * t + k;
-            if (v < p.V && (xg[v] & 1u)) w |= 1u << k;
-        }
-        xb[t] = w;
-    }
-    for (int v = tid; v < p.V; v += kThreads) dl[v] = 0;
-    __syncthreads();
-    const uint64_t *prow = reinterpret_cast<const uint64_t *>(lits) + (size_t)pidx[b] * p.C;
-    for (int c = tid; c < p.C; c += kThreads) {
-        const uint64_t w = prow[c];
-        int var[MSAT_LIT_SLOTS];
-        bool val[MSAT_LIT_SLOTS];
-        bool old = false;
-#pragma unroll
-        for (int j = 0; j < MSAT_LIT_SLOTS; ++j) {
-            const uint32_t code = (uint32_t)(w >> (16 * j)) & 0xFFFFu;
-            var[j] = code >= MSAT_LIT_ABSENT ? -1 : (int)(code >> 1);  // NULL / ABSENT: no variable, false
-            val[j] = var[j] >= 0 && ((((xb[var[j] >> 5] >> (var[j] & 31)) & 1u) ^ (code & 1u)) != 0u);
-            old = old || val[j];
-        }
-#pragma unroll
-        for (int j = 0; j < MSAT_LIT_SLOTS; ++j) {
-            const int v = var[j];
-            if (v < 0) continue;
-            bool dup = false;
-#pragma unroll
-            for (int k = 0; k < j; ++k) dup = dup || (var[k] == v);
-            if (dup) continue;
-            bool nw = false;
-#pragma unroll
-            for (int k = 0; k < MSAT_LIT_SLOTS; ++k) nw = nw || (var[k] >= 0 && (val[k] != (var[k] == v)));
-            if (nw != old) atomicAdd(&dl[v], old ? 1 : -1);
-        }
-    }
-    __syncthreads();
-    if (deltas)
-        for (int v = tid; v < p.V; v += kThreads) deltas[(size_t)b * p.V + v] = dl[v];
-    for (int i = tid; i < p.A; i += kThreads) {
-        int best = 0, bi = p.M;
-        const int lo = agent_lo(p, i), n = agent_size(p, i);
-        for (int j = 0; j < n; ++j) {
-            const int d = dl[lo + j];
-            if (d < best) {
-                best = d;
-                bi = j;
-            }
-        }
-        labels[(size_t)b * p.A + i] = ((float)best < tau) ? bi : p.M;
-    }
-}
-
-// ------------------------------------------------- BC corrupted experts ----
-// behavioral_cloning.py:121-130 for a batch: sample s is expert row src_row[s] (clamped into the table)
-// with n = min(level, V) distinct variables flipped.  The n variables are Floyd's sample of [0, V): for
-// i = 0..n-1, j = V - n + i, t = mulhi32(philox(counter, s, i).x, j + 1) in [0, j]; take t unless it is
-// already taken, then j (never taken before: earlier picks are <= j - 1).  Every pick flips once, so
-// "taken" is dst != src at that position and the sample needs no scratch.  One thread per sample: the
-// draws of a sample are sequential and each thread reads back only bytes it stored itself (a one-off
-// preprocessing pass over N x NUM_SAMPLES_PER_EXPERT rows of V bytes).
-__global__ void __launch_bounds__(256)
-bc_corrupt_kernel(const uint8_t *__restrict__ src, int n_src, const int32_t *__restrict__ src_row, int S, int V,
-                  int n, uint64_t seed, uint64_t ctr, uint8_t *__restrict__ dst) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= S) return;
-    const uint8_t *x = src + (size_t)min(max(src_row[s], 0), n_src - 1) * V;
-    uint8_t *y = dst + (size_t)s * V;
-    for (int v = 0; v < V; ++v) y[v] = x[v];
-    for (int i = 0; i < n; ++i) {
-        const int j = V - n + i;
-        const uint4 q = philox4x32_10(make_uint4((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)s, (uint32_t)i),
-                                      (uint32_t)seed, (uint32_t)(seed >> 32));
-        const int t = (int)mulhi32(q.x, (uint32_t)j + 1u);
-        const int pick = y[t] != x[t] ? j : t;
-        MSAT_DCHECK(pick, V);
-        y[pick] = x[pick] ^ 1u;
-    }
-}
-
-// single-agent SatEnv clause features [is_sat, is_unsat, 1] (sat_env.py:143-160)
-__global__ void clause_sat_features_kernel(int BC, const uint8_t *__restrict__ sat, float *__restrict__ f) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= BC) return;
-    const float s = (float)sat[t];
-    f[3 * (size_t)t + 0] = s;
-    f[3 * (size_t)t + 1] = 1.0f - s;
-    f[3 * (size_t)t + 2] = 1.0f;
-}
-
 // ------------------------------------------------------------- host glue ----
-
-static int make_params(const msat_env_desc *d, EnvParams *p) {
-    MSAT_REQUIRE(d != nullptr, "desc is NULL");
-    MSAT_REQUIRE(d->num_envs >= 0, "num_envs < 0");
-    MSAT_REQUIRE(d->num_vars >= 1 && d->num_vars <= 32000, "num_vars %d out of [1,32000]", d->num_vars);
-    MSAT_REQUIRE(d->num_clauses >= 1, "num_clauses %d < 1", d->num_clauses);
-    MSAT_REQUIRE(d->clause_width >= 1 && d->clause_width <= 3, "clause_width %d out of [1,3]", d->clause_width);
-    MSAT_REQUIRE(d->num_agents >= 1 && d->num_agents <= 1000, "num_agents %d out of [1,1000]", d->num_agents);
-    MSAT_REQUIRE(d->action_mode == 0 || d->action_mode == 1, "action_mode %d", d->action_mode);
-    MSAT_REQUIRE(d->reward_mode >= 0 && d->reward_mode <= 2, "reward_mode %d", d->reward_mode);
-    MSAT_REQUIRE(d->obs_dtype == MSAT_OBS_I32 || d->obs_dtype == MSAT_OBS_I8, "obs_dtype %d", d->obs_dtype);
-    MSAT_REQUIRE(d->num_problems >= 1, "num_problems %d < 1", d->num_problems);
-    p->B = d->num_envs;
-    p->V = d->num_vars;
-    p->C = d->num_clauses;
-    p->K = d->clause_width;
-    p->A = d->num_agents;
-    p->base = p->V / p->A;
-    p->rem = p->V % p->A;
-    p->M = p->base + (p->rem > 0 ? 1 : 0);
-    MSAT_REQUIRE(d->max_vars_per_agent == p->M, "max_vars_per_agent %d != ceil(V/A)=%d",
-                 d->max_vars_per_agent, p->M);
-    p->WV = 2 * ((p->V + 63) / 64);
-    p->WC = 2 * ((p->C + 63) / 64);
-    p->D = 2 * p->V + p->C;
-    p->max_steps = d->max_steps;
-    p->action_mode = d->action_mode;
-    p->reward_mode = d->reward_mode;
-    p->N = d->num_problems;
-    p->r_clause = d->r_clause;
-    p->r_sat = d->r_sat;
-    p->gamma = d->gamma;
-    const char *ab = getenv("MARLSAT_ABLATE");
-    p->ablate = ab ? atoi(ab) : 0;
-    p->dbg_obs = p->dbg_assign = p->dbg_sat = p->dbg_ntrue = p->dbg_actions = 0;
-    p->rq_mode = 0;
-    p->rq_cap = rq_capacity(p->B);
-    p->rq_serial = 0;
-    return MSAT_OK;
-}
 
 // The reset-queue role of a launch on state st (EnvParams::rq_mode): the autoreset step of the sparse reward mode
 // consumes and produces it; every other state-modifying launch clears the entries of the envs it touches.
 static int set_reset_queue(EnvParams *p, const msat_env_state *st, int mode) {
     p->rq_mode = 0;
+    p->rq_cap = rq_capacity(p->B);
     if (st->reset_queue == nullptr || mode == kModeObs) return MSAT_OK;
     MSAT_REQUIRE((reinterpret_cast<uintptr_t>(st->reset_queue) & 15) == 0, "reset_queue must be 16-byte aligned");
     if (MSAT_DEBUG_BUILD)
@@ -1538,18 +1223,6 @@ static void set_dbg_extents(EnvParams *p, const msat_env_state *st, const int32_
     p->dbg_sat = dbg_extent(st->clause_sat, 1);
     p->dbg_ntrue = dbg_extent(st->clause_ntrue, 1);
     p->dbg_actions = dbg_extent(actions, 4);
-}
-
-static int check_state(const msat_env_state *st) {
-    MSAT_REQUIRE(st != nullptr, "state is NULL");
-    MSAT_REQUIRE(st->assign && st->clause_sat && st->num_unsat && st->step && st->done && st->problem_idx,
-                 "a required state pointer is NULL");
-    return MSAT_OK;
-}
-
-static int check_pool(const msat_pool *pool) {
-    MSAT_REQUIRE(pool != nullptr && pool->lits && pool->rel && pool->nbr, "pool (lits/rel/nbr) is NULL");
-    return MSAT_OK;
 }
 
 // MARLSAT_ENV_THREADS (64 / 128 / 256 / 512), read once per process: forces both width rules below; 0 if unset
@@ -1593,6 +1266,37 @@ static int env_delta_threads(const EnvParams &p, int obs_dtype) {
     return env_threads(p);
 }
 
+// f(ObsT{}, std::integral_constant<int, W>{}) for the launch's obs dtype and its workgroup size W: the one of
+// T0, Ts... equal to T, or the last of them
+template <int T0, int... Ts, typename F>
+static void for_width_dtype(int T, int obs_dtype, F f) {
+    if constexpr (sizeof...(Ts) > 0) {
+        if (T != T0) return for_width_dtype<Ts...>(T, obs_dtype, f);
+    }
+    if (obs_dtype == MSAT_OBS_I32)
+        f(int32_t{}, std::integral_constant<int, T0>{});
+    else
+        f(int8_t{}, std::integral_constant<int, T0>{});
+}
+
+// One (MODE, ObsT, T) launch: shadow::env_kernel for a step with an obs shadow (modes 1 and 2 alone have that
+// kernel), env_kernel otherwise
+template <int MODE, typename ObsT, int T>
+static void launch_env_kernel(int grid, size_t lds, hipStream_t s, const EnvParams &p, const msat_pool &pool,
+                              const msat_env_state &st, const int32_t *actions, const uint8_t *mask,
+                              const int32_t *npidx, const uint8_t *nassign, uint64_t seed, uint64_t ctr,
+                              const msat_step_out &o, void *obs, const ObsShadowArg &sa) {
+    if constexpr (MODE == kModeStep || MODE == kModeStepAutoReset) {
+        if (sa.rows != nullptr) {
+            hipLaunchKernelGGL((shadow::env_kernel<MODE, ObsT, T>), dim3(grid), dim3(T), lds, s, p, pool, st, actions,
+                               mask, npidx, nassign, seed, ctr, o, (ObsT *)obs, sa.rows, sa.g);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((env_kernel<MODE, ObsT, T>), dim3(grid), dim3(T), lds, s, p, pool, st, actions, mask, npidx,
+                       nassign, seed, ctr, o, (ObsT *)obs);
+}
+
 template <int MODE>
 static int launch_env(const EnvParams &p, const msat_env_desc *d, const msat_pool *pool,
                       const msat_env_state *st, const int32_t *actions, const uint8_t *mask,
@@ -1617,36 +1321,10 @@ static int launch_env(const EnvParams &p, const msat_env_desc *d, const msat_poo
     if (int rc = set_reset_queue(&pd, st, MODE)) return rc;
     // the reset workgroups of a queue-consuming launch come first (block ids 0 .. cap - 1)
     const int grid = p.B + (pd.rq_mode == 1 ? pd.rq_cap : 0);
-#define MSAT_ENV_LAUNCH(TT)                                                                                        \
-    if constexpr (MODE == kModeStep || MODE == kModeStepAutoReset) {                                               \
-        if (sa.rows != nullptr) {                                                                                  \
-            if (d->obs_dtype == MSAT_OBS_I32)                                                                      \
-                hipLaunchKernelGGL((shadow::env_kernel<MODE, int32_t, TT>), dim3(grid), dim3(TT), lds, s, pd,      \
-                                   *pool, *st, actions, mask, npidx, nassign, seed, ctr, o, (int32_t *)obs, sa.rows, \
-                                   sa.g);                                                                          \
-            else                                                                                                   \
-                hipLaunchKernelGGL((shadow::env_kernel<MODE, int8_t, TT>), dim3(grid), dim3(TT), lds, s, pd,       \
-                                   *pool, *st, actions, mask, npidx, nassign, seed, ctr, o, (int8_t *)obs, sa.rows,  \
-                                   sa.g);                                                                          \
-            return check_launch("env_kernel");                                                                     \
-        }                                                                                                          \
-    }                                                                                                              \
-    if (d->obs_dtype == MSAT_OBS_I32)                                                                              \
-        hipLaunchKernelGGL((env_kernel<MODE, int32_t, TT>), dim3(grid), dim3(TT), lds, s, pd, *pool, *st, actions, \
-                           mask, npidx, nassign, seed, ctr, o, (int32_t *)obs);                                    \
-    else                                                                                                           \
-        hipLaunchKernelGGL((env_kernel<MODE, int8_t, TT>), dim3(grid), dim3(TT), lds, s, pd, *pool, *st, actions,  \
-                           mask, npidx, nassign, seed, ctr, o, (int8_t *)obs);
-    if (T == 64) {
-        MSAT_ENV_LAUNCH(64)
-    } else if (T == 128) {
-        MSAT_ENV_LAUNCH(128)
-    } else if (T == 512) {
-        MSAT_ENV_LAUNCH(512)
-    } else {
-        MSAT_ENV_LAUNCH(256)
-    }
-#undef MSAT_ENV_LAUNCH
+    for_width_dtype<64, 128, 512, 256>(T, d->obs_dtype, [&](auto obs_t, auto width) {
+        launch_env_kernel<MODE, decltype(obs_t), decltype(width)::value>(grid, lds, s, pd, *pool, *st, actions, mask,
+                                                                         npidx, nassign, seed, ctr, o, obs, sa);
+    });
     return check_launch("env_kernel");
 }
 
@@ -1712,20 +1390,10 @@ static int launch_groups(int G, const msat_env_desc *descs, const msat_pool *poo
     MSAT_REQUIRE(lds <= 160 * 1024, "env needs %zu B of LDS (> 160 KiB)", lds);
     gs.total = total;
     if (total == 0) return MSAT_OK;
-    const int gT = group_threads(total);
-#define MSAT_GROUP_LAUNCH(TT)                                                                                      \
-    if (descs[0].obs_dtype == MSAT_OBS_I32)                                                                        \
-        hipLaunchKernelGGL((env_group_kernel<MODE, int32_t, TT>), dim3(total), dim3(TT), lds, s, gs, seed, ctr);   \
-    else                                                                                                           \
-        hipLaunchKernelGGL((env_group_kernel<MODE, int8_t, TT>), dim3(total), dim3(TT), lds, s, gs, seed, ctr);
-    if (gT == 1024) {
-        MSAT_GROUP_LAUNCH(1024)
-    } else if (gT == 512) {
-        MSAT_GROUP_LAUNCH(512)
-    } else {
-        MSAT_GROUP_LAUNCH(256)
-    }
-#undef MSAT_GROUP_LAUNCH
+    for_width_dtype<1024, 512, 256>(group_threads(total), descs[0].obs_dtype, [&](auto obs_t, auto width) {
+        hipLaunchKernelGGL((env_group_kernel<MODE, decltype(obs_t), decltype(width)::value>), dim3(total),
+                           dim3(decltype(width)::value), lds, s, gs, seed, ctr);
+    });
     return check_launch("env_group_kernel");
 }
 
@@ -1771,40 +1439,13 @@ extern "C" int msat_env_group_launch_threads(int32_t total_envs) {
 
 extern "C" size_t msat_reset_queue_words(int32_t num_envs) { return num_envs < 0 ? 0 : rq_words(num_envs); }
 
-extern "C" int msat_pool_pack(const int32_t *lits, int32_t num_problems, int32_t num_clauses,
-                              int32_t clause_width, int32_t num_vars, uint16_t *pool,
-                              int32_t *err_flag, void *stream) {
-    MSAT_REQUIRE(lits && pool && err_flag, "NULL pointer");
-    MSAT_REQUIRE(clause_width >= 1 && clause_width <= 3, "clause_width %d out of [1,3]", clause_width);
-    MSAT_REQUIRE(num_problems >= 0 && num_clauses >= 1, "bad pool dims");
-    const int NC = num_problems * num_clauses;
-    if (NC == 0) return MSAT_OK;
-    hipLaunchKernelGGL(pool_pack_kernel, dim3((NC + 255) / 256), dim3(256), 0, (hipStream_t)stream, lits,
-                       NC, clause_width, num_vars, pool, err_flag);
-    return check_launch("pool_pack_kernel");
-}
-
-extern "C" int msat_pool_agent_tables(const msat_env_desc *desc, const uint16_t *lits, uint32_t *rel, uint32_t *nbr,
-                                      void *stream) {
-    EnvParams p;
-    int rc = make_params(desc, &p);
-    if (rc) return rc;
-    MSAT_REQUIRE(lits && rel && nbr, "NULL pointer");
-    const size_t lds = (size_t)p.A * (p.WC + p.WV) * 4;
-    MSAT_REQUIRE(lds <= 160 * 1024, "agent tables need %zu B of LDS (> 160 KiB)", lds);
-    hipLaunchKernelGGL(agent_tables_kernel, dim3(p.N), dim3(kThreads), lds, (hipStream_t)stream, p, lits, rel, nbr);
-    return check_launch("agent_tables_kernel");
-}
-
 extern "C" int msat_env_reset(const msat_env_desc *desc, const msat_pool *pool,
                               const msat_env_state *state, const uint8_t *reset_mask,
                               const int32_t *new_problem_idx, const uint8_t *new_assign,
                               uint64_t seed, uint64_t rng_counter, void *obs, void *stream) {
     EnvParams p;
-    int rc = make_params(desc, &p);
-    if (rc) return rc;
+    if (int rc = env_entry(desc, state, pool, &p)) return rc;
     if (p.B == 0) return MSAT_OK;
-    if ((rc = check_state(state)) || (rc = check_pool(pool))) return rc;
     return launch_env<kModeReset>(p, desc, pool, state, nullptr, reset_mask, new_problem_idx, new_assign,
                                   seed, rng_counter, nullptr, obs, (hipStream_t)stream);
 }
@@ -1813,18 +1454,9 @@ extern "C" int msat_env_step(const msat_env_desc *desc, const msat_pool *pool,
                              const msat_env_state *state, const int32_t *actions, int32_t autoreset,
                              const int32_t *new_problem_idx, const uint8_t *new_assign, uint64_t seed,
                              uint64_t rng_counter, const msat_step_out *out, void *obs, void *stream) {
-    EnvParams p;
-    int rc = make_params(desc, &p);
-    if (rc) return rc;
-    if (p.B == 0) return MSAT_OK;
-    if ((rc = check_state(state)) || (rc = check_pool(pool))) return rc;
-    MSAT_REQUIRE(actions, "NULL actions");
-    MSAT_REQUIRE(out && out->reward && out->done && out->solved, "NULL step outputs");
-    if (autoreset)
-        return launch_env<kModeStepAutoReset>(p, desc, pool, state, actions, nullptr, new_problem_idx,
-                                              new_assign, seed, rng_counter, out, obs, (hipStream_t)stream);
-    return launch_env<kModeStep>(p, desc, pool, state, actions, nullptr, nullptr, nullptr, seed,
-                                 rng_counter, out, obs, (hipStream_t)stream);
+    // a step without an obs shadow: the same checks in the same order, and launch_env's plain kernels
+    return msat_env_step_delta(desc, pool, state, actions, autoreset, new_problem_idx, new_assign, seed, rng_counter,
+                               out, obs, nullptr, 0, stream);
 }
 
 extern "C" size_t msat_obs_shadow_words(const msat_env_desc *desc) {
@@ -1861,90 +1493,10 @@ extern "C" int msat_env_step_delta(const msat_env_desc *desc, const msat_pool *p
 extern "C" int msat_env_obs(const msat_env_desc *desc, const msat_pool *pool, const msat_env_state *state,
                             void *obs, void *stream) {
     EnvParams p;
-    int rc = make_params(desc, &p);
-    if (rc) return rc;
+    if (int rc = env_entry(desc, state, pool, &p)) return rc;
     if (p.B == 0) return MSAT_OK;
-    if ((rc = check_state(state)) || (rc = check_pool(pool))) return rc;
     MSAT_REQUIRE(obs, "NULL obs");
     return launch_env<kModeObs>(p, desc, pool, state, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, obs,
                                 (hipStream_t)stream);
 }
 
-extern "C" int msat_env_masks(const msat_env_desc *desc, const msat_pool *pool,
-                              const msat_env_state *state, int32_t *agent_clause_masks,
-                              int32_t *agent_neighbor_masks, int32_t *literal_to_agent_idx,
-                              void *stream) {
-    EnvParams p;
-    int rc = make_params(desc, &p);
-    if (rc) return rc;
-    if ((rc = check_state(state)) || (rc = check_pool(pool))) return rc;
-    if (p.B == 0) return MSAT_OK;
-    hipLaunchKernelGGL(env_masks_kernel, dim3(p.B), dim3(kThreads), 0, (hipStream_t)stream, p, *pool,
-                       state->problem_idx, agent_clause_masks, agent_neighbor_masks, literal_to_agent_idx);
-    return check_launch("env_masks_kernel");
-}
-
-extern "C" int msat_clause_features(const msat_env_desc *desc, const msat_env_state *state,
-                                    float *clause_features, void *stream) {
-    EnvParams p;
-    int rc = make_params(desc, &p);
-    if (rc) return rc;
-    MSAT_REQUIRE(state && state->clause_sat && state->clause_ntrue && clause_features,
-                 "clause_features needs clause_sat, clause_ntrue and an output");
-    const int BC = p.B * p.C;
-    if (BC == 0) return MSAT_OK;
-    hipLaunchKernelGGL(clause_features_kernel, dim3((BC + 255) / 256), dim3(256), 0, (hipStream_t)stream, BC,
-                       state->clause_sat, state->clause_ntrue, clause_features);
-    return check_launch("clause_features_kernel");
-}
-
-extern "C" int msat_bc_greedy_labels(const msat_env_desc *desc, const uint16_t *lits, const int32_t *problem_idx,
-                                     const uint8_t *assign, float tau, int32_t *labels, int32_t *deltas,
-                                     void *stream) {
-    EnvParams p;
-    int rc = make_params(desc, &p);
-    if (rc) return rc;
-    if (p.B == 0) return MSAT_OK;
-    MSAT_REQUIRE(lits && problem_idx && assign && labels, "NULL pointer");
-    const size_t lds = ((size_t)p.WV + p.V) * 4;
-    MSAT_REQUIRE(lds <= 160 * 1024, "bc labels need %zu B of LDS", lds);
-    hipLaunchKernelGGL(bc_labels_kernel, dim3(p.B), dim3(kThreads), lds, (hipStream_t)stream, p, lits, problem_idx,
-                       assign, tau, labels, deltas);
-    return check_launch("bc_labels_kernel");
-}
-
-extern "C" int msat_bc_corrupt(const uint8_t *src, int32_t n_src, const int32_t *src_row, int32_t S, int32_t V,
-                               int32_t level, uint64_t seed, uint64_t counter, uint8_t *dst, void *stream) {
-    MSAT_REQUIRE(S >= 0, "bc_corrupt: S %d < 0", S);
-    MSAT_REQUIRE(V >= 1, "bc_corrupt: V %d < 1", V);
-    MSAT_REQUIRE(level >= 0, "bc_corrupt: level %d < 0", level);
-    MSAT_REQUIRE(n_src >= 1, "bc_corrupt: n_src %d < 1", n_src);
-    if (S == 0) return MSAT_OK;
-    MSAT_REQUIRE(src && src_row && dst, "bc_corrupt: NULL pointer");
-    hipLaunchKernelGGL(bc_corrupt_kernel, dim3((S + 255) / 256), dim3(256), 0, (hipStream_t)stream, src, n_src,
-                       src_row, S, V, std::min(level, V), seed, counter, dst);
-    return check_launch("bc_corrupt_kernel");
-}
-
-extern "C" int msat_clause_sat_features(const msat_env_desc *desc, const msat_env_state *state,
-                                        float *clause_features, void *stream) {
-    EnvParams p;
-    int rc = make_params(desc, &p);
-    if (rc) return rc;
-    MSAT_REQUIRE(state && state->clause_sat && clause_features, "NULL pointer");
-    const int BC = p.B * p.C;
-    if (BC == 0) return MSAT_OK;
-    hipLaunchKernelGGL(clause_sat_features_kernel, dim3((BC + 255) / 256), dim3(256), 0, (hipStream_t)stream, BC,
-                       state->clause_sat, clause_features);
-    return check_launch("clause_sat_features_kernel");
-}
-
-extern "C" int msat_static_var_features(const uint16_t *pool, int32_t num_problems, int32_t num_vars,
-                                        int32_t num_clauses, float *var_features, void *stream) {
-    MSAT_REQUIRE(pool && var_features, "NULL pointer");
-    MSAT_REQUIRE(num_vars >= 1 && num_vars <= 32000 && num_clauses >= 1, "bad dims");
-    if (num_problems == 0) return MSAT_OK;
-    hipLaunchKernelGGL(static_var_features_kernel, dim3(num_problems), dim3(kThreads),
-                       (size_t)num_vars * 8, (hipStream_t)stream, pool, num_vars, num_clauses, var_features);
-    return check_launch("static_var_features_kernel");
-}

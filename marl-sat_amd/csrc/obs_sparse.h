@@ -6,6 +6,7 @@
 // same functions on the host against a brute-force get_obs.  On the device the chunked tasks (sparse_task,
 // sparse_entry) serve int8 observations; int32 ones scatter their changed elements one by one (scatter_obs in
 // env_kernels.hip), which uses obs_elem (debug read-back) and the carried task index of this file.
+// env_kernels.hip, the step / reset / obs kernel family, is this header's only device user.
 #pragma once
 
 #include <stdint.h>
@@ -18,7 +19,7 @@
 
 namespace msat {
 
-// What the observation layout needs of EnvParams (env:345-398): row i, element k: k < V own vars, V <= k < V + C
+// What the observation layout needs of EnvParams (env_params.h; env:345-398): row i, element k: k < V own vars, V <= k < V + C
 // clause status, k >= V + C neighbour vars; agent i owns [i*base + min(i, rem), + base + (i < rem)).
 struct ObsGeom {
     int V, C, A, D;  // D = 2V + C
