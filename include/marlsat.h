@@ -31,6 +31,8 @@
  *                               src/learners/mappo_gnn_sat_learner.py:150-164
  *   msat_walksat             <- solve_one (pysat Glucose3 -> one .sol per .cnf)  src/utils/sat_solver.py:5-29;
  *                               here a batched WalkSAT/SKC local search
+ *   msat_solve_track / _pick <- the first-solve bookkeeping of evaluate_policy  src/runners/mappo_runner.py:30-73
+ *                               (+ best-so-far assignment, flip count and the choice among restarts)
  *   msat_gae                 <- _calculate_gae + global normalisation
  *                               src/learners/mappo_gnn_sat_learner.py:504-532
  */
@@ -290,6 +292,56 @@ int msat_walksat(const uint16_t *lits, int32_t num_problems, int32_t num_vars, i
                  int32_t max_flips, uint32_t noise_p32, uint64_t seed, uint64_t counter, int32_t form,
                  uint8_t *assign_out, uint8_t *solved, int32_t *flips, int32_t *num_unsat, void *stream);
 int msat_walksat_forms(void); /* number of kernel forms; form 0 = automatic, 1..n force one */
+
+/* The policy solver's search record (marlsat/solvers/policy.py): what a policy search remembers per env row
+ * while it steps B envs of V variables.  It replaces the three jnp.where selects per step with which the
+ * reference's evaluation loop remembers the first solve (src/runners/mappo_runner.py, runner:30-73), and adds
+ * what that loop drops: the best assignment of a row that never solves, and the number of variables flipped.
+ * All arrays are caller-allocated device memory; the entry points only enqueue. */
+typedef struct msat_solve_state {
+    uint8_t *prev_x;      /* (B,V) the assignment after the last tracked step                       */
+    uint8_t *best_x;      /* (B,V) the assignment of the record below (the solution once solved)    */
+    int32_t *best_unsat;  /* (B,)  least number of unsatisfied clauses seen (0 once solved)         */
+    int32_t *best_step;   /* (B,)  the step that record was set at (0 = the reset assignment)       */
+    int32_t *first_solve; /* (B,)  step of the first solve, -1 = not solved                         */
+    int32_t *flips;       /* (B,)  variables flipped up to the first solve (or up to the last step) */
+    int32_t *unsolved;    /* (1,)  number of rows with first_solve < 0 after the call               */
+} msat_solve_state;
+
+/* msat_solve_track_init: the record of the reset assignment.  assign (B,V) u8, num_unsat (B,) i32 (the env
+ * state's arrays after a reset).  Per row: prev_x = best_x = assign, best_unsat = num_unsat, best_step = 0,
+ * flips = 0, first_solve = 0 where num_unsat == 0, else -1.
+ * msat_solve_track: call after env step number `step` (1-based) with the state's assignment and the step's
+ * outputs solved (B,) u8 and num_unsat (B,) i32.  For a row with first_solve < 0:
+ *   flips += popcount(prev_x ^ assign) over the row, then prev_x = assign;
+ *   solved != 0:                  first_solve = step, best_step = step, best_unsat = 0, best_x = assign;
+ *   else num_unsat < best_unsat:  best_unsat = num_unsat, best_step = step, best_x = assign (strictly fewer: a
+ *                                 tie keeps the earlier record).
+ * A row with first_solve >= 0 is frozen: no field of it changes, whatever the env does afterwards.
+ * After either call unsolved[0] is the number of rows with first_solve < 0, recomputed from first_solve by a
+ * single-workgroup launch behind the row kernel (the caller never zeroes it; every word has one writer, so two
+ * identical runs leave identical words).
+ * B == 0: unsolved[0] = 0, nothing else.  MSAT_EBADARG: B < 0, V < 1, step < 1, a NULL state or unsolved word,
+ * any other NULL pointer with B > 0.
+ * (Additive entry points: msat_version() stays 3, no struct changed.) */
+int msat_solve_track_init(int32_t B, int32_t V, const uint8_t *assign, const int32_t *num_unsat,
+                          const msat_solve_state *state, void *stream);
+int msat_solve_track(int32_t B, int32_t V, int32_t step, const uint8_t *assign, const uint8_t *solved,
+                     const int32_t *num_unsat, const msat_solve_state *state, void *stream);
+
+/* One winner per instance among its tries: instance p of P owns the rows p * tries .. p * tries + tries - 1 of
+ * state (P * tries rows of V variables; prev_x and unsolved are not read).  Order (csrc/solve_pick.h):
+ *   1. a solved row (first_solve >= 0) beats an unsolved one;
+ *   2. among solved rows: fewest first_solve, then fewest flips, then lowest try;
+ *   3. among unsolved rows: least best_unsat, then least best_step, then lowest try.
+ * Outputs of the winner, (P,) each: solved u8, try_out (its index within the instance), steps = first_solve
+ * (-1 where unsolved), flips, best_unsat, best_step; x (P,V) u8 = its best_x.
+ * P == 0: MSAT_OK without a launch.  MSAT_EBADARG: P < 0, tries < 1, V < 1, P * tries > INT32_MAX, a NULL
+ * pointer with P > 0.
+ * (Additive entry point: msat_version() stays 3, no struct changed.) */
+int msat_solve_pick(int32_t P, int32_t tries, int32_t V, const msat_solve_state *state, uint8_t *solved,
+                    int32_t *try_out, int32_t *steps, int32_t *flips, int32_t *best_unsat, int32_t *best_step,
+                    uint8_t *x, void *stream);
 
 /* Single-agent SatEnv clause features [is_sat, is_unsat, 1] (B,C,3) (src/envs/sat_env.py:143-160). */
 int msat_clause_sat_features(const msat_env_desc *desc, const msat_env_state *state,

@@ -259,6 +259,25 @@ int msat_split_dlogits(const float *dlogits, int32_t SA, int32_t M, float *dflip
 /* ---- policy / loss / optimiser (learner:397-403, :597-650; mappo_runner.py:198) ---- */
 int msat_sample_actions(const float *logits, int32_t R, int32_t W, int32_t greedy, uint64_t seed,
                         uint64_t counter, int32_t *action, float *logp, void *stream);
+/* Gumbel-max sampling at a temperature (the policy solver's sampled restarts, marlsat/solvers/policy.py):
+ * every logit is first rounded to fp32 as logits[j] * inv_temperature (inv_temperature = 1 / T); from there
+ * the arithmetic is msat_sample_actions' with greedy = 0 -- the same Philox counters (counter lo, counter hi,
+ * row, j) keyed by seed, the Gumbel noise added at finite slots only, the lowest index on ties, -inf slots
+ * never chosen beside a finite one, and action 0 with log-prob 0 for a row with no finite logit.  logp is the
+ * log-probability of the action under the tempered distribution softmax(logits * inv_temperature).  The
+ * outputs are bitwise those of msat_sample_actions on logits pre-multiplied in fp32; at inv_temperature = 1
+ * those of msat_sample_actions on the logits themselves.
+ * inv_temperature <= 0, NaN or inf, R < 0, W < 1, or a NULL pointer with R > 0: MSAT_EBADARG.
+ * (Additive entry point: msat_version() stays 3, no struct changed.) */
+int msat_sample_actions_t(const float *logits, int32_t R, int32_t W, float inv_temperature, uint64_t seed,
+                          uint64_t counter, int32_t *action, float *logp, void *stream);
+/* msat_sample_actions_t for a piece of a larger batch: row r of the call draws the Philox stream of row
+ * row0 + r, counters (counter lo, counter hi, row0 + r, j), so a batch cut into pieces of any size samples, row
+ * for row, what one call on the whole batch samples (the policy solver's slabs).  row0 = 0 is
+ * msat_sample_actions_t.  Additionally row0 < 0 or row0 + R > 2^32 - 1: MSAT_EBADARG.
+ * (Additive entry point: msat_version() stays 3, no struct changed.) */
+int msat_sample_actions_from(const float *logits, int32_t R, int32_t W, int64_t row0, float inv_temperature,
+                             uint64_t seed, uint64_t counter, int32_t *action, float *logp, void *stream);
 int msat_ppo_loss(const float *logits, int32_t S, int32_t A, int32_t M, int32_t action_mode,
                   int32_t base_sz, int32_t rem, const int32_t *action, const float *old_logp,
                   const float *gae, const float *value, const float *old_value, const float *targets,

@@ -240,33 +240,46 @@ __global__ void split_dlogits_kernel(const float *__restrict__ dl, int SA, int M
 
 // -------------------------------------------------------------- categorical --
 // One wave per distribution row of width W (logits may hold -inf).
-__device__ __forceinline__ void row_softmax_stats(const float *__restrict__ lg, int W, float &mx, float &lse) {
+// TEMPERED: every logit is first rounded to fp32 as lg[j] * inv_t (msat_sample_actions_t); the product is a
+// value of its own before any other operation sees it (-ffp-contract=off: never fused into the subtraction
+// or the Gumbel add), so the row is bitwise the plain one on logits pre-multiplied in fp32.
+template <bool TEMPERED>
+__device__ __forceinline__ float row_logit(const float *__restrict__ lg, int j, float inv_t) {
+    return TEMPERED ? lg[j] * inv_t : lg[j];
+}
+
+template <bool TEMPERED = false>
+__device__ __forceinline__ void row_softmax_stats(const float *__restrict__ lg, int W, float &mx, float &lse,
+                                                  float inv_t = 1.0f) {
     const int lane = threadIdx.x & 63;
     float m = -INFINITY;
-    for (int j = lane; j < W; j += 64) m = fmaxf(m, lg[j]);
+    for (int j = lane; j < W; j += 64) m = fmaxf(m, row_logit<TEMPERED>(lg, j, inv_t));
     m = wave_max_f32(m);
     float s = 0.f;
-    for (int j = lane; j < W; j += 64) s += __expf(lg[j] - m);
+    for (int j = lane; j < W; j += 64) s += __expf(row_logit<TEMPERED>(lg, j, inv_t) - m);
     s = wave_sum_f32(s);
     mx = m;
     lse = m + __logf(s);
 }
 
-// Gumbel-max sample (greedy=0) or argmax (greedy=1) + log_prob of the action.
+// Gumbel-max sample (greedy=0) or argmax (greedy=1) + log_prob of the action.  TEMPERED (greedy = 0 only):
+// the same row code on lg[j] * inv_t, log_prob under the tempered distribution.  Row r draws the Philox stream of
+// row row0 + r (0 in msat_sample_actions: a piece of a larger batch samples what the whole batch would).
+template <bool TEMPERED>
 __global__ void __launch_bounds__(256)
-sample_kernel(const float *__restrict__ logits, int R, int W, int greedy, uint64_t seed, uint64_t ctr,
-              int32_t *__restrict__ action, float *__restrict__ logp) {
+sample_kernel(const float *__restrict__ logits, int R, int W, int greedy, float inv_t, uint32_t row0, uint64_t seed,
+              uint64_t ctr, int32_t *__restrict__ action, float *__restrict__ logp) {
     const int lane = threadIdx.x & 63;
     for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < R; r += gridDim.x * 4) {
         const float *lg = logits + (size_t)r * W;
         float mx, lse;
-        row_softmax_stats(lg, W, mx, lse);
+        row_softmax_stats<TEMPERED>(lg, W, mx, lse, inv_t);
         float best = -INFINITY;
         int bi = 0x7FFFFFFF;
         for (int j = lane; j < W; j += 64) {
-            float v = lg[j];
+            float v = row_logit<TEMPERED>(lg, j, inv_t);
             if (!greedy && v > -INFINITY) {
-                const uint4 q = philox4x32_10(make_uint4((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)r, (uint32_t)j),
+                const uint4 q = philox4x32_10(make_uint4((uint32_t)ctr, (uint32_t)(ctr >> 32), row0 + (uint32_t)r, (uint32_t)j),
                                               (uint32_t)seed, (uint32_t)(seed >> 32));
                 const float u = ((float)(q.x >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1)
                 v += -__logf(-__logf(u));
@@ -289,7 +302,7 @@ sample_kernel(const float *__restrict__ logits, int R, int W, int greedy, uint64
             action[r] = bi;
             // a row with no finite logit (mode-1 padded variable slot) stores log-prob 0: distrax gives
             // NaN there (-inf - logsumexp(-inf)), which would poison the PPO ratio
-            logp[r] = mx > -INFINITY ? lg[bi] - lse : 0.f;
+            logp[r] = mx > -INFINITY ? row_logit<TEMPERED>(lg, bi, inv_t) - lse : 0.f;
         }
     }
 }
@@ -679,9 +692,37 @@ extern "C" int msat_sample_actions(const float *logits, int32_t R, int32_t W, in
                                    uint64_t counter, int32_t *action, float *logp, void *stream) {
     MSAT_REQUIRE(logits && action && logp && W >= 1, "bad sample args");
     if (!R) return MSAT_OK;
-    hipLaunchKernelGGL(sample_kernel, dim3(std::min(8192, (R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, R,
-                       W, greedy, seed, counter, action, logp);
+    hipLaunchKernelGGL(sample_kernel<false>, dim3(std::min(8192, (R + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       logits, R, W, greedy, 1.0f, 0u, seed, counter, action, logp);
     return check_launch("sample_kernel");
+}
+
+static int sample_tempered(const char *who, const float *logits, int32_t R, int32_t W, int64_t row0,
+                           float inv_temperature, uint64_t seed, uint64_t counter, int32_t *action, float *logp,
+                           void *stream) {
+    MSAT_REQUIRE(inv_temperature > 0.0f && inv_temperature < INFINITY, "%s: inv_temperature %g outside (0, inf)", who,
+                 (double)inv_temperature);
+    MSAT_REQUIRE(R >= 0, "%s: R %d < 0", who, R);
+    MSAT_REQUIRE(W >= 1, "%s: W %d < 1", who, W);
+    MSAT_REQUIRE(row0 >= 0 && row0 + R <= (int64_t)UINT32_MAX, "%s: rows [%lld, %lld) outside [0, 2^32)", who,
+                 (long long)row0, (long long)row0 + R);
+    if (!R) return MSAT_OK;
+    MSAT_REQUIRE(logits && action && logp, "%s: NULL pointer", who);
+    hipLaunchKernelGGL(sample_kernel<true>, dim3(std::min(8192, (R + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       logits, R, W, 0, inv_temperature, (uint32_t)row0, seed, counter, action, logp);
+    return check_launch("sample_kernel<tempered>");
+}
+
+extern "C" int msat_sample_actions_t(const float *logits, int32_t R, int32_t W, float inv_temperature, uint64_t seed,
+                                     uint64_t counter, int32_t *action, float *logp, void *stream) {
+    return sample_tempered("sample_actions_t", logits, R, W, 0, inv_temperature, seed, counter, action, logp, stream);
+}
+
+extern "C" int msat_sample_actions_from(const float *logits, int32_t R, int32_t W, int64_t row0,
+                                        float inv_temperature, uint64_t seed, uint64_t counter, int32_t *action,
+                                        float *logp, void *stream) {
+    return sample_tempered("sample_actions_from", logits, R, W, row0, inv_temperature, seed, counter, action, logp,
+                           stream);
 }
 
 extern "C" int msat_ppo_loss(const float *logits, int32_t S, int32_t A, int32_t M, int32_t action_mode,

@@ -68,6 +68,18 @@ class StepOutC(ctypes.Structure):
     ]
 
 
+class SolveStateC(ctypes.Structure):
+    _fields_ = [
+        ("prev_x", c_void_p),
+        ("best_x", c_void_p),
+        ("best_unsat", c_void_p),
+        ("best_step", c_void_p),
+        ("first_solve", c_void_p),
+        ("flips", c_void_p),
+        ("unsolved", c_void_p),
+    ]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -114,6 +126,9 @@ def _load():
              P, P, P],
         ),
         "msat_walksat_forms": (c_int32, []),
+        "msat_solve_track_init": (c_int32, [c_int32, c_int32, P, P, POINTER(SolveStateC), P]),
+        "msat_solve_track": (c_int32, [c_int32, c_int32, c_int32, P, P, P, POINTER(SolveStateC), P]),
+        "msat_solve_pick": (c_int32, [c_int32, c_int32, c_int32, POINTER(SolveStateC), P, P, P, P, P, P, P, P]),
         "msat_static_var_features": (c_int32, [P, c_int32, c_int32, c_int32, P, P]),
         "msat_reset_queue_words": (c_size_t, [c_int32]),
         "msat_env_launch_threads": (c_int32, [POINTER(EnvDesc)]),
@@ -181,6 +196,8 @@ def _load():
     sig["msat_mask_var_logits"] = (I, [P, I, I, I, I, I, P])
     sig["msat_split_dlogits"] = (I, [P, I, I, P, P, P])
     sig["msat_sample_actions"] = (I, [P, I, I, I, U, U, P, P, P])
+    sig["msat_sample_actions_t"] = (I, [P, I, I, F, U, U, P, P, P])
+    sig["msat_sample_actions_from"] = (I, [P, I, I, ctypes.c_int64, F, U, U, P, P, P])
     sig["msat_ppo_loss"] = (I, [P, I, I, I, I, I, I, P, P, P, P, P, P, F, F, F, F, I, P, P, P, P, P])
     sig["msat_bc_loss"] = (I, [P, I, I, I, P, I, P, P, P, P])
     sig["msat_gemm_f64acc"] = (I, [P, I, I, P, I, I, P, I, I, I, I, I, P])
@@ -282,6 +299,8 @@ EXPORTED = (
     "msat_mask_var_logits",
     "msat_split_dlogits",
     "msat_sample_actions",
+    "msat_sample_actions_t",
+    "msat_sample_actions_from",
     "msat_ppo_loss",
     "msat_bc_loss",
     "msat_adam",
@@ -308,6 +327,9 @@ EXPORTED = (
     "msat_bc_corrupt",
     "msat_walksat",
     "msat_walksat_forms",
+    "msat_solve_track_init",
+    "msat_solve_track",
+    "msat_solve_pick",
     "msat_env_step_grouped",
     "msat_env_obs",
     "msat_env_masks",

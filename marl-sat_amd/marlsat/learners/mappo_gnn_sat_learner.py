@@ -207,9 +207,19 @@ class MAPPOLearner:
     def _batch(self, pidx: torch.Tensor, x: torch.Tensor, critic_only: bool = False, totals=None) -> GraphBatch:
         return assemble(self.tpl, self.pool.packed, self.svf, pidx.contiguous(), x.contiguous(), critic_only, totals)
 
-    def policy(self, st: SATState, key: Key, greedy: bool = False, critic: bool = True):
+    def policy(self, st: SATState, key: Key, greedy: bool = False, critic: bool = True, temperature: float = 1.0,
+               row_offset: Optional[int] = None):
         """Actor (+ critic) on the current states (learner:391-403): actions, log_probs, values.
-        greedy: argmax actions (evaluate_policy, runner:38-46); critic=False skips the value head."""
+        greedy: argmax actions (evaluate_policy, runner:38-46); critic=False skips the value head.
+        temperature != 1.0 (sampling only): Gumbel-max on logits / temperature, log_probs under that
+        distribution (msat_sample_actions_t).  row_offset (sampling only; the policy solver's slabs): env b
+        draws the stream of env row_offset + b of one undivided batch, whatever the chunk size
+        (msat_sample_actions_from).  With neither, the calls are exactly what they were."""
+        if not (0.0 < float(temperature) < math.inf):
+            raise ValueError(f"temperature must be in (0, inf), got {temperature}")
+        tempered = not greedy and (float(temperature) != 1.0 or row_offset is not None)
+        if greedy and row_offset is not None:
+            row_offset = None  # argmax draws nothing
         B = st.num_envs
         A, M = self.A, self.M
         act = torch.empty((B, A) if self.mode == 0 else (B, A, M), dtype=torch.int32, device=self.device)
@@ -223,6 +233,20 @@ class MAPPOLearner:
             if critic:
                 val[b0:b1] = value
             rows = logits.numel() // W
+            if tempered:
+                inv_t = 1.0 / float(temperature)
+                if row_offset is None:
+                    _lib.check(L_.msat_sample_actions_t(logits.data_ptr(), rows, W, inv_t, key.seed,
+                                                        (key.counter << 16) + c, act[b0:b1].data_ptr(),
+                                                        logp[b0:b1].data_ptr(), _lib.stream_ptr(self.device)),
+                               "msat_sample_actions_t")
+                else:  # rows per env = rows // (b1 - b0); no chunk index: the row names its stream
+                    _lib.check(L_.msat_sample_actions_from(logits.data_ptr(), rows, W,
+                                                           (int(row_offset) + b0) * (rows // (b1 - b0)), inv_t,
+                                                           key.seed, key.counter << 16, act[b0:b1].data_ptr(),
+                                                           logp[b0:b1].data_ptr(), _lib.stream_ptr(self.device)),
+                               "msat_sample_actions_from")
+                continue
             _lib.check(L_.msat_sample_actions(logits.data_ptr(), rows, W, 1 if greedy else 0, key.seed,
                                               (key.counter << 16) + c, act[b0:b1].data_ptr(), logp[b0:b1].data_ptr(),
                                               _lib.stream_ptr(self.device)), "msat_sample_actions")
