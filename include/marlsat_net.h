@@ -123,6 +123,20 @@ int msat_assemble_graph_batch(
     const int32_t *eoff, const int32_t *poff, const int32_t *gv, const int32_t *gc, float *vfeat, float *cfeat,
     float *cdeg, int32_t *slots, int32_t *ptr, int32_t *inc, int32_t *g_vbase, int32_t *g_nv, int32_t *g_cbase, int32_t *g_nc,
     int32_t Nv, int32_t nnz, void *stream);
+/* The same for graphs g0 .. g0+G-1 of each sample's instance (0 <= g0, G >= 1, g0 + G <= A+1):
+ * g0 = 0 is msat_assemble_graph_batch bit for bit; g0 = 1, G = A is the actor-only batch (the agents'
+ * masked encoders, learner:243-276, without the critic's unmasked one, :340-342).  The templates keep
+ * graph 0 first and instance-relative row ids, so the kernel rebases t_ptr values, the var rows in
+ * t_slots and the clause rows in t_inc by graph g0's starts; sample_bases, Nv and nnz are those of the
+ * G graphs alone (msat_graph_bases over the per-instance counts of graphs g0 .. g0+G-1), and
+ * g_vbase / g_nv / g_cbase / g_nc get G entries per sample. */
+int msat_assemble_graph_batch_from(
+    int32_t S, int32_t g0, int32_t G, int32_t A, int32_t V, int32_t C, const int32_t *inst, const uint8_t *x,
+    const float *svf, const uint16_t *pool, const int32_t *sample_bases, const int32_t *t_vgid, const int32_t *t_cgid,
+    const int32_t *t_slots, const int32_t *t_ptr, const int32_t *t_inc, const int32_t *voff, const int32_t *coff,
+    const int32_t *eoff, const int32_t *poff, const int32_t *gv, const int32_t *gc, float *vfeat, float *cfeat,
+    float *cdeg, int32_t *slots, int32_t *ptr, int32_t *inc, int32_t *g_vbase, int32_t *g_nv, int32_t *g_cbase, int32_t *g_nc,
+    int32_t Nv, int32_t nnz, void *stream);
 
 /* ---- message passing: signed literal gathers (the encoder's A^T M and A M, learner:66-74) ----
  * clause_gather: dst[c] (+)= [sum_{pos slots} src[v][0:H] | sum_{neg slots} src[v][H:2H]],
@@ -248,6 +262,16 @@ int msat_actor_pool_bwd(int32_t H, const int32_t *vbase, const int32_t *nv, cons
                         const int32_t *nc, int32_t G, int32_t S, int32_t A, int32_t M, int32_t base_sz,
                         int32_t rem, int32_t E, const float *dmy, const float *dctx, float *dHp, float *dHn,
                         float *dHc, float *did, void *stream);
+/* The actor pools (learner:287-301) on a batch whose agent i graph is slot ag0 + i of its sample's G
+ * graphs: ag0 = 1 (G = A+1, the two above) or ag0 = 0 (G = A, an actor-only batch). */
+int msat_actor_pool_from(const float *Hp, const float *Hn, const float *Hc, int32_t H, const int32_t *vbase,
+                         const int32_t *nv, const int32_t *cbase, const int32_t *nc, int32_t G, int32_t ag0,
+                         int32_t S, int32_t A, int32_t M, int32_t base_sz, int32_t rem, const float *id_emb,
+                         int32_t E, float *my_emb, float *ctx, void *stream);
+int msat_actor_pool_bwd_from(int32_t H, const int32_t *vbase, const int32_t *nv, const int32_t *cbase,
+                             const int32_t *nc, int32_t G, int32_t ag0, int32_t S, int32_t A, int32_t M,
+                             int32_t base_sz, int32_t rem, int32_t E, const float *dmy, const float *dctx,
+                             float *dHp, float *dHn, float *dHc, float *did, void *stream);
 int msat_bcast_add_relu(float *Q, const float *P, int32_t R, int32_t M, int32_t W, void *stream);
 int msat_group_sum(const float *dQ, int32_t R, int32_t M, int32_t W, float *dP, void *stream);
 int msat_assemble_logits(const float *flip, const float *noop, int32_t SA, int32_t A, int32_t M,

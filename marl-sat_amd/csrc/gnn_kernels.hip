@@ -753,15 +753,17 @@ __global__ void relu_bwd_kernel(float *__restrict__ dy, const float *__restrict_
 }
 
 // ---------------------------------------------------------- batch assembly --
-// Block per sample: instantiate the instance's graph templates at the sample's row
-// bases and compute its node features from the sample's assignment.
+// Block per sample: instantiate graphs g0 .. g0+G-1 of the instance's templates at the sample's row
+// bases and compute its node features from the sample's assignment.  The templates are stored per
+// instance with graph 0 first and instance-relative row ids, so everything read from them is rebased
+// by the skipped graphs' rows (v0, c0) and incidences (eb); g0 = 0 makes all three zero.
 // Debug builds: element extents of every buffer the kernel indexes (dbg_extent), checked at each access.
 struct AsmDbg {
     long long x, svf, pool, t_vgid, t_cgid, t_slots, t_ptr, t_inc, vfeat, cfeat, cdeg, slots, ptr, inc, g_vbase, g_nv,
         g_cbase, g_nc;
 };
 __global__ void __launch_bounds__(256)
-assemble_graph_batch_kernel(int S, int G, int A, int V, int C, const int *__restrict__ inst,
+assemble_graph_batch_kernel(int S, int g0, int G, int A, int V, int C, const int *__restrict__ inst,
                             const uint8_t *__restrict__ x, const float *__restrict__ svf,
                             const uint64_t *__restrict__ pool, const int *__restrict__ sb,
                             const int *__restrict__ t_vgid, const int *__restrict__ t_cgid,
@@ -777,22 +779,25 @@ assemble_graph_batch_kernel(int S, int G, int A, int V, int C, const int *__rest
     const int vr0 = sb[3 * s], cr0 = sb[3 * s + 1], e0 = sb[3 * s + 2];
     const int tv0 = voff[n], tc0 = coff[n], te0 = eoff[n], tp0 = poff[n];
     const int *gvn = gv + (size_t)n * (A + 2), *gcn = gc + (size_t)n * (A + 2);
-    const int nvr = gvn[G], ncr = gcn[G];
-    const int ne = t_ptr[tp0 + nvr];
-    const uint8_t *xs = x + (size_t)s * V;
+    const int v0 = gvn[g0], c0 = gcn[g0];
+    const int nvr = gvn[g0 + G] - v0, ncr = gcn[g0 + G] - c0;
     if (threadIdx.x == 0) {
         MSAT_DCHECK((long long)(s + 1) * V - 1, dbg.x);
-        MSAT_DCHECK((long long)tp0 + nvr, dbg.t_ptr);
+        MSAT_DCHECK((long long)tp0 + v0 + nvr, dbg.t_ptr);
     }
+    const int eb = t_ptr[tp0 + v0];  // the first graph's incidence start in the instance (ge[n][g0])
+    const int ne = t_ptr[tp0 + v0 + nvr] - eb;
+    const uint8_t *xs = x + (size_t)s * V;
     for (int t = threadIdx.x; t < nvr; t += blockDim.x) {
-        MSAT_DCHECK((long long)tv0 + t, dbg.t_vgid);
-        const int gid = t_vgid[tv0 + t];
+        MSAT_DCHECK((long long)tv0 + v0 + t, dbg.t_vgid);
+        const int gid = t_vgid[tv0 + v0 + t];
         MSAT_DCHECK(gid, V);
         MSAT_DCHECK((long long)(vr0 + t) * 8 + 7, dbg.vfeat);
         MSAT_DCHECK(((long long)n * V + gid) * 3 + 2, dbg.svf);
         float *f = vfeat + (size_t)(vr0 + t) * 8;
         const float *sv = svf + ((size_t)n * V + gid) * 3;
-        const int pb = t_ptr[tp0 + t], pe = t_ptr[tp0 + t + 1];
+        const int pb = t_ptr[tp0 + v0 + t], pe = t_ptr[tp0 + v0 + t + 1];
+        MSAT_DCHECK(pb - eb, ne + 1);
         if (pe > pb) MSAT_DCHECK((long long)te0 + pe - 1, dbg.t_inc);
         MSAT_DCHECK((long long)vr0 + t, dbg.ptr);
         int nneg = 0;
@@ -805,28 +810,30 @@ assemble_graph_batch_kernel(int S, int G, int A, int V, int C, const int *__rest
         f[5] = (float)nneg;
         f[6] = 0.0f;
         f[7] = 0.0f;
-        ptr[vr0 + t] = e0 + pb;
+        ptr[vr0 + t] = e0 + (pb - eb);
     }
     for (int e = threadIdx.x; e < ne; e += blockDim.x) {
-        MSAT_DCHECK((long long)te0 + e, dbg.t_inc);
+        MSAT_DCHECK((long long)te0 + eb + e, dbg.t_inc);
         MSAT_DCHECK((long long)e0 + e, dbg.inc);
-        const int ent = t_inc[te0 + e];
-        inc[e0 + e] = ((cr0 + (ent >> 1)) << 1) | (ent & 1);
+        const int ent = t_inc[te0 + eb + e];
+        MSAT_DCHECK((ent >> 1) - c0, ncr);  // a graph's incidences name its own clause rows
+        inc[e0 + e] = ((cr0 + ((ent >> 1) - c0)) << 1) | (ent & 1);
     }
     for (int t = threadIdx.x; t < ncr; t += blockDim.x) {
-        MSAT_DCHECK((long long)tc0 + t, dbg.t_cgid);
-        MSAT_DCHECK((long long)(tc0 + t) * 3 + 2, dbg.t_slots);
+        MSAT_DCHECK((long long)tc0 + c0 + t, dbg.t_cgid);
+        MSAT_DCHECK((long long)(tc0 + c0 + t) * 3 + 2, dbg.t_slots);
         MSAT_DCHECK((long long)(cr0 + t) * 3 + 2, dbg.slots);
         MSAT_DCHECK((long long)(cr0 + t) * 3 + 2, dbg.cfeat);
         if (cdeg) MSAT_DCHECK((long long)(cr0 + t) * 4 + 3, dbg.cdeg);
-        const int gcid = t_cgid[tc0 + t];
+        const int gcid = t_cgid[tc0 + c0 + t];
         MSAT_DCHECK(gcid, C);
         MSAT_DCHECK((long long)n * C + gcid, dbg.pool);
         int npos = 0, nneg = 0;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const int sl = t_slots[(size_t)(tc0 + t) * 3 + j];
-            slots[(size_t)(cr0 + t) * 3 + j] = sl < 0 ? -1 : (((vr0 + (sl >> 1)) << 1) | (sl & 1));
+            const int sl = t_slots[(size_t)(tc0 + c0 + t) * 3 + j];
+            if (sl >= 0) MSAT_DCHECK((sl >> 1) - v0, nvr);  // a graph's slots name its own var rows
+            slots[(size_t)(cr0 + t) * 3 + j] = sl < 0 ? -1 : (((vr0 + ((sl >> 1) - v0)) << 1) | (sl & 1));
             npos += sl >= 0 && !(sl & 1);
             nneg += sl >= 0 && (sl & 1);
         }
@@ -854,10 +861,10 @@ assemble_graph_batch_kernel(int S, int G, int A, int V, int C, const int *__rest
         MSAT_DCHECK((long long)s * G + g, dbg.g_nv);
         MSAT_DCHECK((long long)s * G + g, dbg.g_cbase);
         MSAT_DCHECK((long long)s * G + g, dbg.g_nc);
-        g_vbase[s * G + g] = vr0 + gvn[g];
-        g_nv[s * G + g] = gvn[g + 1] - gvn[g];
-        g_cbase[s * G + g] = cr0 + gcn[g];
-        g_nc[s * G + g] = gcn[g + 1] - gcn[g];
+        g_vbase[s * G + g] = vr0 + (gvn[g0 + g] - v0);
+        g_nv[s * G + g] = gvn[g0 + g + 1] - gvn[g0 + g];
+        g_cbase[s * G + g] = cr0 + (gcn[g0 + g] - c0);
+        g_nc[s * G + g] = gcn[g0 + g + 1] - gcn[g0 + g];
     }
     if (s == 0 && threadIdx.x == 0) {
         MSAT_DCHECK(Nv, dbg.ptr);
@@ -1162,9 +1169,9 @@ extern "C" int msat_gru_ln_bwd_g4(const float *dy, int32_t ldy, const float *g4,
                                dln_bias, dbi, dbh_n, nullptr, 0, 0, nullptr, partial, R, H, accumulate_ln, stream);
 }
 
-extern "C" int msat_assemble_graph_batch(
-    int32_t S, int32_t G, int32_t A, int32_t V, int32_t C, const int32_t *inst, const uint8_t *x, const float *svf,
-    const uint16_t *pool, const int32_t *sample_bases, const int32_t *t_vgid, const int32_t *t_cgid,
+extern "C" int msat_assemble_graph_batch_from(
+    int32_t S, int32_t g0, int32_t G, int32_t A, int32_t V, int32_t C, const int32_t *inst, const uint8_t *x,
+    const float *svf, const uint16_t *pool, const int32_t *sample_bases, const int32_t *t_vgid, const int32_t *t_cgid,
     const int32_t *t_slots, const int32_t *t_ptr, const int32_t *t_inc, const int32_t *voff, const int32_t *coff,
     const int32_t *eoff, const int32_t *poff, const int32_t *gv, const int32_t *gc, float *vfeat, float *cfeat,
     float *cdeg, int32_t *slots, int32_t *ptr, int32_t *inc, int32_t *g_vbase, int32_t *g_nv, int32_t *g_cbase, int32_t *g_nc,
@@ -1173,18 +1180,31 @@ extern "C" int msat_assemble_graph_batch(
                      coff && eoff && poff && gv && gc && vfeat && cfeat && slots && ptr && inc && g_vbase && g_nv &&
                      g_cbase && g_nc,
                  "NULL pointer");
-    MSAT_REQUIRE(G >= 1 && G <= A + 1, "G must be 1 (critic only) or A+1");
+    MSAT_REQUIRE(S >= 0 && A >= 1 && g0 >= 0 && G >= 1 && g0 <= A && G <= A + 1 - g0,
+                 "graphs g0 .. g0+G-1 must lie in 0 .. A (G = 1 critic only, A+1 full; g0 = 1, G = A actor only)");
     if (!S) return MSAT_OK;
     const AsmDbg dbg{dbg_extent(x, 1),       dbg_extent(svf, 4),     dbg_extent(pool, 8),    dbg_extent(t_vgid, 4),
                      dbg_extent(t_cgid, 4),  dbg_extent(t_slots, 4), dbg_extent(t_ptr, 4),   dbg_extent(t_inc, 4),
                      dbg_extent(vfeat, 4),   dbg_extent(cfeat, 4),   dbg_extent(cdeg, 4),    dbg_extent(slots, 4),
                      dbg_extent(ptr, 4),     dbg_extent(inc, 4),     dbg_extent(g_vbase, 4), dbg_extent(g_nv, 4),
                      dbg_extent(g_cbase, 4), dbg_extent(g_nc, 4)};
-    hipLaunchKernelGGL(assemble_graph_batch_kernel, dim3(S), dim3(256), 0, (hipStream_t)stream, S, G, A, V, C, inst, x,
-                       svf, reinterpret_cast<const uint64_t *>(pool), sample_bases, t_vgid, t_cgid, t_slots, t_ptr,
+    hipLaunchKernelGGL(assemble_graph_batch_kernel, dim3(S), dim3(256), 0, (hipStream_t)stream, S, g0, G, A, V, C, inst,
+                       x, svf, reinterpret_cast<const uint64_t *>(pool), sample_bases, t_vgid, t_cgid, t_slots, t_ptr,
                        t_inc, voff, coff, eoff, poff, gv, gc, vfeat, cfeat, cdeg, slots, ptr, inc, g_vbase, g_nv, g_cbase,
                        g_nc, Nv, nnz, dbg);
     return check_launch("assemble_graph_batch_kernel");
+}
+
+extern "C" int msat_assemble_graph_batch(
+    int32_t S, int32_t G, int32_t A, int32_t V, int32_t C, const int32_t *inst, const uint8_t *x, const float *svf,
+    const uint16_t *pool, const int32_t *sample_bases, const int32_t *t_vgid, const int32_t *t_cgid,
+    const int32_t *t_slots, const int32_t *t_ptr, const int32_t *t_inc, const int32_t *voff, const int32_t *coff,
+    const int32_t *eoff, const int32_t *poff, const int32_t *gv, const int32_t *gc, float *vfeat, float *cfeat,
+    float *cdeg, int32_t *slots, int32_t *ptr, int32_t *inc, int32_t *g_vbase, int32_t *g_nv, int32_t *g_cbase, int32_t *g_nc,
+    int32_t Nv, int32_t nnz, void *stream) {
+    return msat_assemble_graph_batch_from(S, 0, G, A, V, C, inst, x, svf, pool, sample_bases, t_vgid, t_cgid, t_slots,
+                                          t_ptr, t_inc, voff, coff, eoff, poff, gv, gc, vfeat, cfeat, cdeg, slots, ptr,
+                                          inc, g_vbase, g_nv, g_cbase, g_nc, Nv, nnz, stream);
 }
 
 extern "C" int msat_relu(float *x, size_t n, void *stream) {

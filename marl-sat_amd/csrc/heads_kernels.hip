@@ -118,10 +118,10 @@ critic_pool_bwd_kernel(const float *__restrict__ Hp, const float *__restrict__ H
 // ctx (S*A, 5H+E) = [mean own (2H) | mean nbr (2H) | mean clauses (H) | id embedding (E)].
 __global__ void __launch_bounds__(256)
 actor_pool_kernel(const float *__restrict__ Hp, const float *__restrict__ Hn, const float *__restrict__ Hc, int H,
-                  GraphRef gr, int A, int M, int base_sz, int rem, const float *__restrict__ id_emb, int E,
+                  GraphRef gr, int ag0, int A, int M, int base_sz, int rem, const float *__restrict__ id_emb, int E,
                   float *__restrict__ my_emb, float *__restrict__ ctx) {
     const int sa = blockIdx.x, s = sa / A, i = sa - s * A;
-    const int gid = s * gr.G + 1 + i;
+    const int gid = s * gr.G + ag0 + i;  // ag0: slot of agent 0's graph in a sample (1 full batch, 0 actor only)
     const int vb = gr.vbase[gid], nv = gr.nv[gid], cb = gr.cbase[gid], nc = gr.nc[gid];
     const int nown = base_sz + (i < rem ? 1 : 0);
     const int CW = 5 * H + E;
@@ -155,11 +155,11 @@ actor_pool_kernel(const float *__restrict__ Hp, const float *__restrict__ Hn, co
 }
 
 __global__ void __launch_bounds__(256)
-actor_pool_bwd_kernel(int H, GraphRef gr, int A, int M, int base_sz, int rem, int E, const float *__restrict__ dmy,
-                      const float *__restrict__ dctx, float *__restrict__ dHp, float *__restrict__ dHn,
-                      float *__restrict__ dHc, float *__restrict__ did) {
+actor_pool_bwd_kernel(int H, GraphRef gr, int ag0, int A, int M, int base_sz, int rem, int E,
+                      const float *__restrict__ dmy, const float *__restrict__ dctx, float *__restrict__ dHp,
+                      float *__restrict__ dHn, float *__restrict__ dHc, float *__restrict__ did) {
     const int sa = blockIdx.x, s = sa / A, i = sa - s * A;
-    const int gid = s * gr.G + 1 + i;
+    const int gid = s * gr.G + ag0 + i;
     const int vb = gr.vbase[gid], nv = gr.nv[gid], cb = gr.cbase[gid], nc = gr.nc[gid];
     const int nown = base_sz + (i < rem ? 1 : 0);
     const int CW = 5 * H + E;
@@ -620,26 +620,46 @@ extern "C" int msat_critic_pool_bwd(const float *Hp, const float *Hn, const floa
     return check_launch("critic_pool_bwd_kernel");
 }
 
+extern "C" int msat_actor_pool_from(const float *Hp, const float *Hn, const float *Hc, int32_t H, const int32_t *vbase,
+                                    const int32_t *nv, const int32_t *cbase, const int32_t *nc, int32_t G, int32_t ag0,
+                                    int32_t S, int32_t A, int32_t M, int32_t base_sz, int32_t rem, const float *id_emb,
+                                    int32_t E, float *my_emb, float *ctx, void *stream) {
+    MSAT_REQUIRE(Hp && Hn && Hc && vbase && nv && cbase && nc && id_emb && my_emb && ctx && S >= 0 && A >= 1 &&
+                     (ag0 == 0 || ag0 == 1) && G == A + ag0,
+                 "bad actor_pool args");
+    if (!S) return MSAT_OK;
+    hipLaunchKernelGGL(actor_pool_kernel, dim3(S * A), dim3(256), 0, (hipStream_t)stream, Hp, Hn, Hc, H,
+                       make_gr(vbase, nv, cbase, nc, G), ag0, A, M, base_sz, rem, id_emb, E, my_emb, ctx);
+    return check_launch("actor_pool_kernel");
+}
+
 extern "C" int msat_actor_pool(const float *Hp, const float *Hn, const float *Hc, int32_t H, const int32_t *vbase,
                                const int32_t *nv, const int32_t *cbase, const int32_t *nc, int32_t G, int32_t S,
                                int32_t A, int32_t M, int32_t base_sz, int32_t rem, const float *id_emb, int32_t E,
                                float *my_emb, float *ctx, void *stream) {
-    MSAT_REQUIRE(Hp && Hn && Hc && id_emb && my_emb && ctx && G == A + 1, "bad actor_pool args");
+    return msat_actor_pool_from(Hp, Hn, Hc, H, vbase, nv, cbase, nc, G, 1, S, A, M, base_sz, rem, id_emb, E, my_emb,
+                                ctx, stream);
+}
+
+extern "C" int msat_actor_pool_bwd_from(int32_t H, const int32_t *vbase, const int32_t *nv, const int32_t *cbase,
+                                        const int32_t *nc, int32_t G, int32_t ag0, int32_t S, int32_t A, int32_t M,
+                                        int32_t base_sz, int32_t rem, int32_t E, const float *dmy, const float *dctx,
+                                        float *dHp, float *dHn, float *dHc, float *did, void *stream) {
+    MSAT_REQUIRE(vbase && nv && cbase && nc && dmy && dctx && dHp && dHn && dHc && did && S >= 0 && A >= 1 &&
+                     (ag0 == 0 || ag0 == 1) && G == A + ag0,
+                 "bad actor_pool_bwd args");
     if (!S) return MSAT_OK;
-    hipLaunchKernelGGL(actor_pool_kernel, dim3(S * A), dim3(256), 0, (hipStream_t)stream, Hp, Hn, Hc, H,
-                       make_gr(vbase, nv, cbase, nc, G), A, M, base_sz, rem, id_emb, E, my_emb, ctx);
-    return check_launch("actor_pool_kernel");
+    hipLaunchKernelGGL(actor_pool_bwd_kernel, dim3(S * A), dim3(256), 0, (hipStream_t)stream, H,
+                       make_gr(vbase, nv, cbase, nc, G), ag0, A, M, base_sz, rem, E, dmy, dctx, dHp, dHn, dHc, did);
+    return check_launch("actor_pool_bwd_kernel");
 }
 
 extern "C" int msat_actor_pool_bwd(int32_t H, const int32_t *vbase, const int32_t *nv, const int32_t *cbase,
                                    const int32_t *nc, int32_t G, int32_t S, int32_t A, int32_t M, int32_t base_sz,
                                    int32_t rem, int32_t E, const float *dmy, const float *dctx, float *dHp, float *dHn,
                                    float *dHc, float *did, void *stream) {
-    MSAT_REQUIRE(dmy && dctx && dHp && dHn && dHc && did && G == A + 1, "bad actor_pool_bwd args");
-    if (!S) return MSAT_OK;
-    hipLaunchKernelGGL(actor_pool_bwd_kernel, dim3(S * A), dim3(256), 0, (hipStream_t)stream, H,
-                       make_gr(vbase, nv, cbase, nc, G), A, M, base_sz, rem, E, dmy, dctx, dHp, dHn, dHc, did);
-    return check_launch("actor_pool_bwd_kernel");
+    return msat_actor_pool_bwd_from(H, vbase, nv, cbase, nc, G, 1, S, A, M, base_sz, rem, E, dmy, dctx, dHp, dHn, dHc,
+                                    did, stream);
 }
 
 extern "C" int msat_bcast_add_relu(float *Q, const float *P, int32_t R, int32_t M, int32_t W, void *stream) {

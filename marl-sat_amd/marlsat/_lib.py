@@ -151,6 +151,7 @@ def _load():
                                             c_int32, P, P])
     I, F, Z, U = c_int32, c_float, c_size_t, c_uint64
     sig["msat_assemble_graph_batch"] = (I, [I, I, I, I, I] + [P] * 26 + [I, I, P])
+    sig["msat_assemble_graph_batch_from"] = (I, [I, I, I, I, I, I] + [P] * 26 + [I, I, P])
     sig["msat_clause_gather"] = (I, [P, I, P, P, I, I, I, I, P])
     sig["msat_var_gather"] = (I, [P, I, P, P, P, I, I, I, I, P])
     sig["msat_split_bf16x3"] = (I, [P, I, I, I, P, P])
@@ -190,6 +191,8 @@ def _load():
     sig["msat_critic_pool_bwd"] = (I, [P, P, P, I, P, P, P, P, I, I, P, P, P, P, P])
     sig["msat_actor_pool"] = (I, [P, P, P, I, P, P, P, P, I, I, I, I, I, I, P, I, P, P, P])
     sig["msat_actor_pool_bwd"] = (I, [I, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P, P, P])
+    sig["msat_actor_pool_from"] = (I, [P, P, P, I, P, P, P, P, I, I, I, I, I, I, I, P, I, P, P, P])
+    sig["msat_actor_pool_bwd_from"] = (I, [I, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, P, P])
     sig["msat_bcast_add_relu"] = (I, [P, P, I, I, I, P])
     sig["msat_group_sum"] = (I, [P, I, I, I, P, P])
     sig["msat_assemble_logits"] = (I, [P, P, I, I, I, I, I, P, P])
@@ -256,6 +259,7 @@ EXPORTED = (
     "msat_moments",
     "msat_standardize",
     "msat_assemble_graph_batch",
+    "msat_assemble_graph_batch_from",
     "msat_clause_gather",
     "msat_var_gather",
     "msat_gru_ln_fused_fwd_x3r",
@@ -293,6 +297,8 @@ EXPORTED = (
     "msat_critic_pool_bwd",
     "msat_actor_pool",
     "msat_actor_pool_bwd",
+    "msat_actor_pool_from",
+    "msat_actor_pool_bwd_from",
     "msat_bcast_add_relu",
     "msat_group_sum",
     "msat_assemble_logits",

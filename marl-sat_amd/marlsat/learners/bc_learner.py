@@ -10,6 +10,8 @@ its own size, :272-276); each minibatch is one gradient of the joint cross-entro
 per-sample terms add) followed by one Adam step at the constant LEARNING_RATE (``optax.adam(LEARNING_RATE)``,
 :225 -- no schedule, ANNEAL_LR is ignored).  Only the encoder, the actor and the agent embedding receive
 gradient: the critic head is not evaluated, so its gradient is exactly 0 and Adam leaves it bitwise unchanged.
+``actor_only=True`` also leaves the critic's graph out of every micro-batch (assemble(actor_only=True)): the
+full batch encodes it, saves its tape and back-propagates an exactly-zero gradient through it.
 
 Action mode 0 only (the reference's labels are mode-0 indices) and a single process (BC is a small offline
 job; MAPPO's tests cover the gradient all-reduce).
@@ -32,7 +34,7 @@ L_ = _lib.lib
 
 class BCLearner:
     def __init__(self, config: dict, env: SATEnv, network: GNNActorCritic, pool: ProblemPool,
-                 micro_bytes: Optional[float] = None):
+                 micro_bytes: Optional[float] = None, actor_only: bool = False):
         if env.action_mode != 0:
             raise ValueError(f"BCLearner: action_mode {env.action_mode} is not supported: the reference's BC labels "
                              f"(compute_joint_labels_parallel_greedy) are mode-0 indices (a local variable or the "
@@ -47,8 +49,9 @@ class BCLearner:
         self.A, self.M = env.num_agents, env.max_vars_per_agent
         self.tpl = DeviceTemplates(build_templates(pool.clauses.cpu().numpy(), env.num_vars, env.num_agents),
                                    env.num_agents, self.device)
-        self.micro, _ = activation_plan(config, self.tpl.mean_full_rows, network.H, network.L, self.MB, 1,
-                                        micro_bytes)
+        self.actor_only = bool(actor_only)
+        rows = self.tpl.mean_actor_rows if self.actor_only else self.tpl.mean_full_rows
+        self.micro, _ = activation_plan(config, rows, network.H, network.L, self.MB, 1, micro_bytes)
         self.svf = pool.static_var_features()
         self.N = 0
         self.data: Optional[Dict[str, torch.Tensor]] = None
@@ -95,12 +98,12 @@ class BCLearner:
         net.grads.zero_()
         bounds = list(range(0, idx.numel(), self.micro)) + [idx.numel()]
         # every micro-batch's row totals from one device -> host read per minibatch (MAPPOLearner.minibatch_grad)
-        sizes = batch_totals(self.tpl, self.data["pidx"].index_select(0, idx.long()), bounds)
+        sizes = batch_totals(self.tpl, self.data["pidx"].index_select(0, idx.long()), bounds, self.actor_only)
         for m0, m1, tot in zip(bounds[:-1], bounds[1:], sizes):
             mi = idx[m0:m1].contiguous()
             S = mi.numel()
             pidx, x, lab = self.gather_rows(mi)
-            gb = assemble(self.tpl, self.pool.packed, self.svf, pidx, x, False, tot)
+            gb = assemble(self.tpl, self.pool.packed, self.svf, pidx, x, False, tot, self.actor_only)
             logits, _, state = net.forward(gb, critic=False, save=True)
             dlog = torch.empty_like(logits)
             rows = torch.empty((2 * S * A,), device=dev)

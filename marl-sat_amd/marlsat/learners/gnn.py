@@ -834,9 +834,10 @@ class GNNActorCritic:
         SA = S * A
         my = torch.empty((SA * M, 2 * H), device=dev)
         ctx = torch.empty((SA, CW), device=dev)
-        _chk(L_.msat_actor_pool(Hp.data_ptr(), Hn.data_ptr(), Hc.data_ptr(), H, *self._gr(b), b.G, S, A, M, self.base,
-                                self.rem, self.p("actor.id_emb").data_ptr(), self.E, my.data_ptr(), ctx.data_ptr(),
-                                self.stream), "actor_pool")
+        # agent i's graph is slot (1 - g0) + i of its sample: after the critic's in a full batch, else first
+        _chk(L_.msat_actor_pool_from(Hp.data_ptr(), Hn.data_ptr(), Hc.data_ptr(), H, *self._gr(b), b.G, 1 - b.g0, S, A,
+                                     M, self.base, self.rem, self.p("actor.id_emb").data_ptr(), self.E, my.data_ptr(),
+                                     ctx.data_ptr(), self.stream), "actor_pool")
         ht.my, ht.ctx = my, ctx
         pp = self._ptr
         if self.mode == 0:
@@ -937,13 +938,23 @@ class GNNActorCritic:
             self._gemm(dP.data_ptr(), 128, pp(w0[2 * H]), 128, 1, pp(dctx, 5 * H), CW, None, SA, self.E, 128)
             self._wgrad(pp(ht.ctx, 5 * H), CW, dP.data_ptr(), 128, pp(gw0[2 * H]), 128, SA, self.E, 128)
         did = torch.empty((SA, self.E), device=dev)
-        _chk(L_.msat_actor_pool_bwd(H, *self._gr(b), b.G, S, A, M, self.base, self.rem, self.E, dmy.data_ptr(),
-                                    dctx.data_ptr(), dHp.data_ptr(), dHn.data_ptr(), dHc.data_ptr(), did.data_ptr(),
-                                    self.stream), "actor_pool_bwd")
+        _chk(L_.msat_actor_pool_bwd_from(H, *self._gr(b), b.G, 1 - b.g0, S, A, M, self.base, self.rem, self.E,
+                                         dmy.data_ptr(), dctx.data_ptr(), dHp.data_ptr(), dHn.data_ptr(),
+                                         dHc.data_ptr(), did.data_ptr(), self.stream), "actor_pool_bwd")
         self._colsum(did.data_ptr(), A * self.E, S, A * self.E, self.g("actor.id_emb").data_ptr())
 
     # ---------------------------------------------------------- top level ----
+    def _check_heads(self, b: GraphBatch, actor: bool, critic: bool, what: str):
+        """The heads a batch can feed: the critic pool reads slot 0 of each sample as graph 0 and the actor pool
+        A slots from graph 1 on, so a head on a batch without its graphs would silently pool the wrong rows."""
+        if critic and b.g0 != 0:
+            raise ValueError(f"{what}: the batch is actor-only (graphs {b.g0}..{b.g0 + b.G - 1}): no critic graph")
+        if actor and b.g0 + b.G != self.A + 1:
+            raise ValueError(f"{what}: the batch holds graphs {b.g0}..{b.g0 + b.G - 1} of 0..{self.A}, not the "
+                             f"agents' (critic-only batch?)")
+
     def forward(self, b: GraphBatch, actor: bool = True, critic: bool = True, save: bool = False):
+        self._check_heads(b, actor, critic, "forward")
         Hp, Hn, Hc, tape = self.encode(b, save)
         ht = HeadTape()
         logits = self.actor_head(b, Hp, Hn, Hc, ht) if actor else None
@@ -953,6 +964,7 @@ class GNNActorCritic:
 
     def backward(self, b: GraphBatch, state, dlogits: Optional[torch.Tensor], dvalue: Optional[torch.Tensor]):
         """Accumulate parameter gradients (self.grads += ...) for upstream grads of logits / value."""
+        self._check_heads(b, dlogits is not None, dvalue is not None, "backward")
         Hp, Hn, Hc, tape, ht = state
         dHp = torch.zeros_like(Hp)
         dHn = torch.zeros_like(Hn)

@@ -152,13 +152,27 @@ class DeviceTemplates:
         self.crit_v = dv(t.gv[:, 1])
         self.crit_c = dv(t.gc[:, 1])
         self.crit_e = dv(t.ge[:, 1])
+        # an actor-only sample: graphs 1..A, the full counts less graph 0's
+        self.actor_v = dv(t.gv[:, -1] - t.gv[:, 1])
+        self.actor_c = dv(t.gc[:, -1] - t.gc[:, 1])
+        self.actor_e = dv(t.ge[:, -1] - t.ge[:, 1])
         self.max_full_rows = int((t.gv[:, -1] + t.gc[:, -1]).max())
         self.mean_full_rows = float((t.gv[:, -1] + t.gc[:, -1]).mean())
+        self.mean_actor_rows = float((t.gv[:, -1] - t.gv[:, 1] + t.gc[:, -1] - t.gc[:, 1]).mean())
+
+    def counts(self, actor_only: bool = False, critic_only: bool = False):
+        """Per-instance (var rows, clause rows, incidences) of one sample's graphs."""
+        if actor_only:
+            return self.actor_v, self.actor_c, self.actor_e
+        if critic_only:
+            return self.crit_v, self.crit_c, self.crit_e
+        return self.full_v, self.full_c, self.full_e
 
 
 @dataclass
 class GraphBatch:
-    """Device row-level graph batch of S samples (G graphs each)."""
+    """Device row-level graph batch of S samples (G graphs each: graphs g0 .. g0+G-1 of the sample's instance;
+    full batch g0 = 0, G = A+1; critic only g0 = 0, G = 1; actor only g0 = 1, G = A)."""
 
     S: int
     G: int
@@ -175,24 +189,30 @@ class GraphBatch:
     nv: torch.Tensor
     cbase: torch.Tensor
     nc: torch.Tensor
+    g0: int = 0  # the first template graph held (1: actor only, agent i's graph is slot i of its sample)
 
 
 def assemble(tpl: DeviceTemplates, pool_packed: torch.Tensor, svf: torch.Tensor, inst: torch.Tensor,
-             x: torch.Tensor, critic_only: bool = False, totals: Optional[Tuple[int, int, int]] = None) -> GraphBatch:
+             x: torch.Tensor, critic_only: bool = False, totals: Optional[Tuple[int, int, int]] = None,
+             actor_only: bool = False) -> GraphBatch:
     """Instantiate the templates for samples (inst (S,), x (S,V) uint8) on the device.  ``totals`` =
     the batch's (var rows, clause rows, incidences) when the caller already knows them (the learner
     plans a minibatch's micro-batches at once, batch_totals): no device -> host read here, so the host
-    keeps queueing work instead of waiting for the GPU to drain."""
-    if totals is not None and critic_only:  # batch_totals plans the full (actor + critic) graphs only
+    keeps queueing work instead of waiting for the GPU to drain.  ``actor_only``: the agents' graphs 1..A
+    without the critic's graph 0 (a batch for logits alone: no value, no dvalue); its ``totals`` come from
+    batch_totals(actor_only=True)."""
+    if actor_only and critic_only:
+        raise ValueError("assemble: actor_only and critic_only are mutually exclusive")
+    if totals is not None and critic_only:  # batch_totals plans the full or the actor-only graphs
         raise ValueError("assemble: planned totals are for the full graphs; critic_only batches size themselves")
     S = int(inst.shape[0])
-    G = 1 if critic_only else tpl.G
+    g0, G = (1, tpl.A) if actor_only else (0, 1 if critic_only else tpl.G)
     dev = inst.device
     inst = inst.to(torch.int32).contiguous()
     # per-sample row bases (exclusive scans of the instances' row counts) and the batch totals
     sb = torch.empty((max(S, 1), 3), dtype=torch.int32, device=dev)
     tot = torch.empty((3,), dtype=torch.int32, device=dev)
-    tv, tc, te = (tpl.crit_v, tpl.crit_c, tpl.crit_e) if critic_only else (tpl.full_v, tpl.full_c, tpl.full_e)
+    tv, tc, te = tpl.counts(actor_only, critic_only)
     _lib.check(_lib.lib.msat_graph_bases(S, inst.data_ptr(), tv.data_ptr(), tc.data_ptr(), te.data_ptr(), sb.data_ptr(),
                                          tot.data_ptr(), _lib.stream_ptr(dev)), "msat_graph_bases")
     Nv, Nc, nnz = tot.tolist() if totals is None else totals  # sizes the outputs
@@ -212,28 +232,30 @@ def assemble(tpl: DeviceTemplates, pool_packed: torch.Tensor, svf: torch.Tensor,
                      torch.empty((S * G,), dtype=torch.int32, device=dev),
                      torch.empty((S * G,), dtype=torch.int32, device=dev),
                      torch.empty((S * G,), dtype=torch.int32, device=dev),
-                     torch.empty((S * G,), dtype=torch.int32, device=dev))
+                     torch.empty((S * G,), dtype=torch.int32, device=dev), g0)
     V = x.shape[1]
     C = pool_packed.shape[1]
-    _lib.check(_lib.lib.msat_assemble_graph_batch(
-        S, G, tpl.A, V, C, inst.data_ptr(), x.data_ptr(), svf.data_ptr(), pool_packed.data_ptr(), sb.data_ptr(),
+    _lib.check(_lib.lib.msat_assemble_graph_batch_from(
+        S, g0, G, tpl.A, V, C, inst.data_ptr(), x.data_ptr(), svf.data_ptr(), pool_packed.data_ptr(), sb.data_ptr(),
         tpl.vgid.data_ptr(), tpl.cgid.data_ptr(), tpl.slots.data_ptr(), tpl.ptr.data_ptr(), tpl.inc.data_ptr(),
         tpl.voff.data_ptr(), tpl.coff.data_ptr(), tpl.eoff.data_ptr(), tpl.poff.data_ptr(), tpl.gv.data_ptr(),
         tpl.gc.data_ptr(), out.vfeat.data_ptr(), out.cfeat.data_ptr(), out.cdeg.data_ptr(), out.slots.data_ptr(), out.ptr.data_ptr(),
         out.inc.data_ptr(), out.vbase.data_ptr(), out.nv.data_ptr(), out.cbase.data_ptr(), out.nc.data_ptr(),
-        Nv, nnz, _lib.stream_ptr(dev)), "msat_assemble_graph_batch")
+        Nv, nnz, _lib.stream_ptr(dev)), "msat_assemble_graph_batch_from")
     return out
 
 
-def batch_totals(tpl: DeviceTemplates, inst: torch.Tensor, bounds: List[int]) -> List[Tuple[int, int, int]]:
-    """(var rows, clause rows, incidences) of the full-sample batches inst[bounds[i]:bounds[i+1]], the
-    totals msat_graph_bases computes for each, from ONE device -> host read for all of them
-    (int64 sums, so an int32 overflow shows up as a total above INT32_MAX, which assemble refuses)."""
+def batch_totals(tpl: DeviceTemplates, inst: torch.Tensor, bounds: List[int],
+                 actor_only: bool = False) -> List[Tuple[int, int, int]]:
+    """(var rows, clause rows, incidences) of the full-sample (or, ``actor_only``, the agents'-graphs-only)
+    batches inst[bounds[i]:bounds[i+1]], the totals msat_graph_bases computes for each, from ONE
+    device -> host read for all of them (int64 sums, so an int32 overflow shows up as a total above
+    INT32_MAX, which assemble refuses)."""
     if len(bounds) < 2:
         return []
     idx = inst.long()
-    cnt = torch.stack((tpl.full_v.index_select(0, idx), tpl.full_c.index_select(0, idx),
-                       tpl.full_e.index_select(0, idx)), 1).to(torch.int64)
+    tv, tc, te = tpl.counts(actor_only)
+    cnt = torch.stack((tv.index_select(0, idx), tc.index_select(0, idx), te.index_select(0, idx)), 1).to(torch.int64)
     cs = torch.cat((torch.zeros((1, 3), dtype=torch.int64, device=cnt.device), torch.cumsum(cnt, 0)))
     at = cs.index_select(0, torch.tensor(bounds, dtype=torch.int64, device=cnt.device))
     return [tuple(int(v) for v in r) for r in (at[1:] - at[:-1]).tolist()]

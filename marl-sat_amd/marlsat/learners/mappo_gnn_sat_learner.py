@@ -170,6 +170,9 @@ class MAPPOLearner:
                                    env.num_agents, self.device)
         self.micro, self.chunk = activation_plan(config, self.tpl.mean_full_rows, network.H, network.L, self.MB,
                                                  self.B, micro_bytes)
+        # the inference chunk of an actor-only batch (policy(actor_only=True)): the same budget over fewer rows
+        _, self.actor_chunk = activation_plan(config, self.tpl.mean_actor_rows, network.H, network.L, self.MB,
+                                              self.B, micro_bytes)
         self.A, self.M = env.num_agents, env.max_vars_per_agent
         self.mode = env.action_mode
         self.svf = pool.static_var_features()
@@ -204,19 +207,27 @@ class MAPPOLearner:
         obs, st = self.env.reset_from_pool(self.pool, self.B, k_reset)
         return RunnerState(st, obs, k_run, 0)
 
-    def _batch(self, pidx: torch.Tensor, x: torch.Tensor, critic_only: bool = False, totals=None) -> GraphBatch:
-        return assemble(self.tpl, self.pool.packed, self.svf, pidx.contiguous(), x.contiguous(), critic_only, totals)
+    def _batch(self, pidx: torch.Tensor, x: torch.Tensor, critic_only: bool = False, totals=None,
+               actor_only: bool = False) -> GraphBatch:
+        return assemble(self.tpl, self.pool.packed, self.svf, pidx.contiguous(), x.contiguous(), critic_only, totals,
+                        actor_only)
 
     def policy(self, st: SATState, key: Key, greedy: bool = False, critic: bool = True, temperature: float = 1.0,
-               row_offset: Optional[int] = None):
+               row_offset: Optional[int] = None, actor_only: bool = False):
         """Actor (+ critic) on the current states (learner:391-403): actions, log_probs, values.
         greedy: argmax actions (evaluate_policy, runner:38-46); critic=False skips the value head.
         temperature != 1.0 (sampling only): Gumbel-max on logits / temperature, log_probs under that
         distribution (msat_sample_actions_t).  row_offset (sampling only; the policy solver's slabs): env b
         draws the stream of env row_offset + b of one undivided batch, whatever the chunk size
-        (msat_sample_actions_from).  With neither, the calls are exactly what they were."""
+        (msat_sample_actions_from).  With neither, the calls are exactly what they were.
+        actor_only (needs critic=False): encode the agents' graphs alone (assemble(actor_only=True)); every
+        row of the encoder is independent of its neighbours, so the logits, actions and log_probs are those of
+        the full batch.  The chunk index enters the sampling counter unless row_offset names the streams, so
+        the chunk stays self.chunk there; greedy or with row_offset the larger actor-only chunk is used."""
         if not (0.0 < float(temperature) < math.inf):
             raise ValueError(f"temperature must be in (0, inf), got {temperature}")
+        if actor_only and critic:
+            raise ValueError("policy: actor_only=True needs critic=False (an actor-only batch has no critic graph)")
         tempered = not greedy and (float(temperature) != 1.0 or row_offset is not None)
         if greedy and row_offset is not None:
             row_offset = None  # argmax draws nothing
@@ -226,9 +237,11 @@ class MAPPOLearner:
         logp = torch.empty(act.shape, dtype=torch.float32, device=self.device)
         val = torch.empty((B,), dtype=torch.float32, device=self.device)
         W = M + 1 if self.mode == 0 else 2
-        for c, b0 in enumerate(range(0, B, self.chunk)):
-            b1 = min(B, b0 + self.chunk)
-            gb = self._batch(st.problem_idx[b0:b1], st.variable_assignments[b0:b1])
+        # the chunk boundaries decide the sampled actions when the chunk index is in the counter (below)
+        chunk = self.actor_chunk if actor_only and (greedy or row_offset is not None) else self.chunk
+        for c, b0 in enumerate(range(0, B, chunk)):
+            b1 = min(B, b0 + chunk)
+            gb = self._batch(st.problem_idx[b0:b1], st.variable_assignments[b0:b1], actor_only=actor_only)
             logits, value, _ = self.net.forward(gb, critic=critic)
             if critic:
                 val[b0:b1] = value

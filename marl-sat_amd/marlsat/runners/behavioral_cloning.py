@@ -130,6 +130,8 @@ def bc_settings(config: Optional[dict]) -> Dict:
             "TAU_IMPROVE": float(bc.get("TAU_IMPROVE", 0.0)),
             "SOL_DATA_DIR": bc.get("SOL_DATA_DIR", "data/uf20-91-answer"),
             "SOLVE_MISSING_EXPERTS": bool(bc.get("SOLVE_MISSING_EXPERTS", False)),
+            # ours (no reference key): micro-batches without the critic's graph (BCLearner(actor_only=True))
+            "ACTOR_ONLY_GRAPHS": bool(bc.get("ACTOR_ONLY_GRAPHS", False)),
             "SAVE_PATH": bc.get("SAVE_PATH", "models/bc_pretrained")}
 
 
@@ -214,7 +216,7 @@ def run(config: Dict, log=print) -> Dict:
     key, k_data = split(key, 2)
     data = preprocess(experts, env, config, seed=k_data.seed, device_corrupt=True)
     train_pool = env.make_pool(data["clauses"])
-    learner = BCLearner(fc, env, net, train_pool)
+    learner = BCLearner(fc, env, net, train_pool, actor_only=bc["ACTOR_ONLY_GRAPHS"])
     learner.set_data(data["problem_idx"], data["assignments"], data["labels"])
     n_upd = int(fc["NUM_UPDATES"])
     gen = torch.Generator().manual_seed(seed)

@@ -92,7 +92,7 @@ def check_temperature(temperature: float, who: str) -> float:
 @torch.no_grad()
 def policy_search(learner, pool, problem_idx, max_steps: int, key, *, greedy: bool = False,
                   temperature: float = 1.0, early_exit: bool = True, trace: Optional[list] = None,
-                  assignments=None, row_offset: Optional[int] = None) -> SearchRecord:
+                  assignments=None, row_offset: Optional[int] = None, actor_only: bool = False) -> SearchRecord:
     """Row b searches instance ``problem_idx[b]`` of ``pool`` for ``max_steps`` steps of ``learner``'s policy
     (argmax when ``greedy``, else sampled at ``temperature``) from a random assignment, with ``evaluate_policy``'s
     key schedule (``search_keys``).  Returns the device ``SearchRecord``.
@@ -101,7 +101,8 @@ def policy_search(learner, pool, problem_idx, max_steps: int, key, *, greedy: bo
     output (``early_exit=False`` runs all steps).  ``trace``: a list that receives the reset assignment and
     every step's actions.  ``assignments`` ((B, V) 0/1): start there instead of the reset draw.  ``row_offset``
     (the slabs of ``solve_pool_with_policy``): row b samples the stream of row ``row_offset + b`` of an
-    undivided batch (``learner.policy``)."""
+    undivided batch (``learner.policy``).  ``actor_only``: every step encodes the agents' graphs alone, without
+    the critic's graph that a search never reads (``learner.policy(actor_only=True)``); the record is the same."""
     env, dev = learner.env, learner.device
     max_steps = int(max_steps)
     if not 1 <= max_steps <= env.max_steps:
@@ -122,7 +123,7 @@ def policy_search(learner, pool, problem_idx, max_steps: int, key, *, greedy: bo
     solved_ptr, step_nun_ptr = out["solved"].data_ptr(), out["num_unsatisfied"].data_ptr()
     for t in range(max_steps):
         act, _, _ = learner.policy(st, k_acts[t], greedy=greedy, critic=False, temperature=temperature,
-                                   row_offset=row_offset)
+                                   row_offset=row_offset, actor_only=actor_only)
         if trace is not None:
             trace.append(act.clone())
         env.step_raw(st, act, autoreset=False, out=out, with_obs=False)
@@ -170,7 +171,7 @@ def _round_outputs(n: int, V: int, device):
 def solve_pool_with_policy(learner, pool, *, tries: int = 8, rounds: int = 2, max_steps: int = None,
                            temperature: float = 1.0, greedy_round: bool = True, finish: str = "walksat",
                            finish_tries: int = 8, finish_flips: int = 100_000, noise: float = 0.5,
-                           max_batch: int = 4096, key=None) -> Dict[str, np.ndarray]:
+                           max_batch: int = 4096, key=None, actor_only: bool = False) -> Dict[str, np.ndarray]:
     """One solution per instance of ``pool`` from ``learner``'s policy, WalkSAT finishing what it leaves.
 
     Round r (``round_plan``) runs, for every instance still unsolved, one greedy try (round 0 with
@@ -185,6 +186,7 @@ def solve_pool_with_policy(learner, pool, *, tries: int = 8, rounds: int = 2, ma
     ``Key(key.seed, key.counter + rounds)``; the lowest solving sample wins.
 
     ``learner``: a ``MAPPOLearner`` over ``pool`` (its network, templates and chunk size are used at any batch).
+    ``actor_only``: passed to every ``policy_search`` (actor-only graph batches; no result changes).
     Returns host arrays over the N instances: ``solved`` bool; ``by`` int8 (0 none, 1 policy, 2 walksat);
     ``solution`` (N, V) uint8 (zeros where unsolved); ``round``, ``try`` int32 of the winning or best try;
     ``steps`` int32 (the policy's first solving step, -1 where it did not solve); ``flips`` int32 (policy
@@ -225,7 +227,7 @@ def solve_pool_with_policy(learner, pool, *, tries: int = 8, rounds: int = 2, ma
             s1 = min(n, s0 + per)
             rec = policy_search(learner, pool, pidx[s0 * T: s1 * T], max_steps, rk, greedy=greedy,
                                 temperature=temperature, assignments=None if x0 is None else x0[s0 * T: s1 * T],
-                                row_offset=s0 * T)
+                                row_offset=s0 * T, actor_only=actor_only)
             rc = rec.c()
             _lib.check(L.msat_solve_pick(s1 - s0, T, V, ctypes.byref(rc), flags[s0:s1].data_ptr(),
                                          ints[0, s0:s1].data_ptr(), ints[1, s0:s1].data_ptr(),

@@ -3,7 +3,8 @@
     python -m marlsat.utils.policy_solver --config configs/MAPPO_CONFIG.yaml [section.KEY=VALUE ...] \\
         --checkpoint experiments/mappo_runs/<run> --cnf-dir data/uf50-218 --sol-dir out/uf50-218 \\
         [--tries 8 --rounds 2 --max-steps 512 --temperature 1.0 --no-greedy-round --finish walksat|none
-         --finish-tries 8 --finish-flips 100000 --noise 0.5 --seed 0 --report report.json --baseline-walksat]
+         --finish-tries 8 --finish-flips 100000 --noise 0.5 --seed 0 --report report.json --baseline-walksat
+         --actor-only]
 
 The network is the config's (``environment`` / ``network`` sections) with the parameters of ``--checkpoint``: a
 run directory (``<dir>/checkpoints/latest_model_0``, ``load_train_state``) or a behavioural-cloning directory
@@ -176,6 +177,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--finish-flips", type=int, default=100_000)
     ap.add_argument("--noise", type=float, default=0.5, help="WalkSAT's random-walk probability")
     ap.add_argument("--max-batch", type=int, default=4096, help="env rows per device batch")
+    ap.add_argument("--actor-only", action="store_true",
+                    help="encode the agents' graphs alone in every search step (no critic graph; same results)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--report", default=None, help="write the JSON report here")
     ap.add_argument("--baseline-walksat", action="store_true", help="also run solve_pool on the same instances")
@@ -192,7 +195,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             load_config(a.config, a.overrides), a.checkpoint, a.cnf_dir, a.sol_dir, baseline=a.baseline_walksat,
             log=print, key=PRNGKey(a.seed), tries=a.tries, rounds=a.rounds, max_steps=a.max_steps,
             temperature=a.temperature, greedy_round=not a.no_greedy_round, finish=a.finish,
-            finish_tries=a.finish_tries, finish_flips=a.finish_flips, noise=a.noise, max_batch=a.max_batch)
+            finish_tries=a.finish_tries, finish_flips=a.finish_flips, noise=a.noise, max_batch=a.max_batch,
+            actor_only=a.actor_only)
     except FileNotFoundError as e:
         print(f"error: {e}", file=sys.stderr)
         return 2
