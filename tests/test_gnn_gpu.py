@@ -79,12 +79,24 @@ def _close_norm(dev, ref, rtol, what):
     _close(dev, ref, 0.0, rtol * max(np.abs(ref[fin]).max(), 1e-12), what)
 
 
-@pytest.mark.parametrize("fuse,path", [(True, "default"), (True, "bf16x3"), (True, "fp32"), (False, "bf16x3"),
-                                       (False, "fp32")])
-@pytest.mark.parametrize("V,C,vpa,H,L,S,mode", CASES)
+# the default path with one switch off (profiles/parity_switch_probe.py's table): the branches gnn.py selects
+# when the fp16x2 families are not all on -- fp32 packed rows under the dual launches, and the non-dual fp16x2
+# products (msat_gemm_wgrad_h2 when only the data gradients fall back, msat_gemm_h2 when only the weight
+# gradients do)
+SINGLE_SWITCH = {"planes0": {"use_planes": False}, "gru_x3": {"use_gru_h2": False},
+                 "dgrad_x3": {"use_dgrad_h2": False}, "wgrad_x3": {"use_wgrad_h2": False}}
+SINGLE_SWITCH_CASES = [(20, 91, 10, 128, 2, 3, 0), (16, 60, 4, 64, 2, 4, 1)]
+assert all(c in CASES for c in SINGLE_SWITCH_CASES)
+
+
+@pytest.mark.parametrize(
+    "V,C,vpa,H,L,S,mode,fuse,path",
+    [c + fp for fp in ((True, "default"), (True, "bf16x3"), (True, "fp32"), (False, "bf16x3"), (False, "fp32"))
+     for c in CASES] + [c + (True, path) for path in SINGLE_SWITCH for c in SINGLE_SWITCH_CASES])
 def test_forward_backward_match_oracle(V, C, vpa, H, L, S, mode, fuse, path, monkeypatch, c_precision):
     """fuse: phi folded into the GRU input matrices (else the reference order); path: the arithmetic
-    (_set_path: fp16x2 / bf16x3 split kernels at H = 128, packed backward rows; fp32 MFMA)."""
+    (_set_path: fp16x2 / bf16x3 split kernels at H = 128, packed backward rows; fp32 MFMA; or the default
+    path with one switch of SINGLE_SWITCH off)."""
     from marlsat.learners.gnn import GNNActorCritic
 
     _set_path(monkeypatch, path, c_precision)
@@ -201,18 +213,21 @@ def _set_path(monkeypatch, path, c_precision):
     """'default': the bench's kernels (phi folded, fp16x2 GRU forward / data / weight gradients with
     dual launches); 'bf16x3': phi folded, the fp16x2 kernels off (the bf16x3 register-A GRU forward,
     bf16x3 data and weight gradients: the fallback wherever fp16's range fails; MARLSAT_PRECISION=bf16x3);
-    'fp32': the reference operation order on fp32 MFMA kernels (MARLSAT_PRECISION=fp32 + FUSE_PHI=0)."""
+    'fp32': the reference operation order on fp32 MFMA kernels (MARLSAT_PRECISION=fp32 + FUSE_PHI=0);
+    a key of SINGLE_SWITCH: 'default' with that one switch off (its kernels' fp32-accurate fallback)."""
     from marlsat.learners.gnn import GNNActorCritic
 
     fast = path != "fp32"
     monkeypatch.setattr(GNNActorCritic, "fuse_phi", fast)
     monkeypatch.setattr(GNNActorCritic, "use_x3", fast)
     monkeypatch.setattr(GNNActorCritic, "use_gru_x3", fast)
-    h2 = path == "default"
+    h2 = path == "default" or path in SINGLE_SWITCH
     for sw in ("use_gru_h2", "use_dgrad_h2", "use_wgrad_h2"):
         monkeypatch.setattr(GNNActorCritic, sw, h2)
-    # the C-side weight-gradient choice (gemm.hip, msat_set_precision)
-    c_precision({"default": "fp16x2", "bf16x3": "bf16x3", "fp32": "fp32"}[path])
+    for sw, v in SINGLE_SWITCH.get(path, {}).items():
+        monkeypatch.setattr(GNNActorCritic, sw, v)
+    # the C-side weight-gradient choice (gemm.hip, msat_set_precision): it follows use_wgrad_h2
+    c_precision({"bf16x3": "bf16x3", "fp32": "fp32", "wgrad_x3": "bf16x3"}.get(path, "fp16x2"))
 
 
 @pytest.mark.parametrize("path", ["default", "bf16x3", "fp32"])
