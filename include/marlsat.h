@@ -15,6 +15,8 @@
  *                               src/envs/multi_agent_sat_env.py:135-144 and :100
  *   msat_pool_agent_tables   <- _compute_observation_maps  src/envs/multi_agent_sat_env.py:99-128
  *                               (hoisted from every reset to once per pool instance)
+ *   msat_pool_generate       <- generate_sat_cnf           src/utils/generate_cnf_dataset.py:5-42
+ *                               (planted k-SAT; Philox draws on the device instead of the host Mersenne Twister)
  *   msat_env_reset           <- SATEnv.reset               src/envs/multi_agent_sat_env.py:158-181
  *                               (+ _compute_observation_maps :99-128, get_obs :345-398)
  *   msat_env_step            <- SATEnv.step_env            src/envs/multi_agent_sat_env.py:225-284
@@ -153,6 +155,34 @@ int msat_pool_pack(const int32_t *lits, int32_t num_problems, int32_t num_clause
  * Reproduces _compute_observation_maps (env:99-128) incl. the literal-0 quirk. */
 int msat_pool_agent_tables(const msat_env_desc *desc, const uint16_t *lits,
                            uint32_t *rel, uint32_t *nbr, void *stream);
+
+/* A pool of planted random k-SAT instances drawn on the device: clauses (N,C,K) int32, signed and 1-based, ready
+ * for msat_pool_pack; planted (N,V) u8, an assignment that satisfies every clause of its instance; attempts (N,)
+ * int32.  The semantics are the reference generator's (src/utils/generate_cnf_dataset.py:5-42): a hidden
+ * assignment; per clause K distinct variables, one uniformly chosen slot forced to agree with the hidden
+ * assignment, a coin for the sign of every other slot.  The draws are Philox4x32-10 words, not the reference's
+ * Mersenne Twister: the same family of instances, not the same bytes.  Instance n depends only on (seed, counter,
+ * n) and the shape, so the first 64 instances of a 128-instance call are the 64-instance call's, and a host replay
+ * reproduces every word (csrc/pool_gen.h holds the arithmetic the kernel runs):
+ *   q(a, b) = philox4x32_10((counter lo, counter hi, n, (a << 24) | b), seed lo, seed hi), attempt a, block b.
+ *   Hidden bits: blocks 0 .. HB-1, HB = ceil(V/128); variable v (0-based) is bit v % 32 of word (v % 128) / 32 of
+ *   block v / 128 (the layout of the reset stream's assignment blocks).
+ *   Clause c: block HB + c, words q0..q3.  Variables: Floyd's sample of K of V as in msat_bc_corrupt: for
+ *   i = 0..K-1, j = V-K+i, t = (q_i * (j+1)) >> 32; slot i takes t unless an earlier slot holds t, then j.  Slots
+ *   stay in pick order.  Anchor slot = ((q3 & 0xFFFF) * K) >> 16: its literal is positive iff its variable's
+ *   hidden bit is 1.  Every other slot i is positive iff bit 16 + i of q3 is 1.  Variable v is literal +-(v + 1).
+ * reject_isolated != 0: an attempt is accepted only if every variable occurs in some clause (an isolated variable
+ * makes the first Adam step non-finite, in the reference and here alike); otherwise the instance's workgroup draws
+ * attempt a + 1, up to max_attempts attempts.  attempts[n] = the accepted attempt, or -1 when none was accepted;
+ * clauses and planted then hold the last attempt.  reject_isolated == 0: every instance is attempt 0.
+ * Enqueues only.  num_problems == 0: MSAT_OK without a launch.  MSAT_EBADARG: num_problems < 0, num_vars outside
+ * [1, 32000], num_clauses < 1, clause_width outside [1, 3] or above num_vars, HB + num_clauses >= 2^24,
+ * max_attempts outside [1, 255], reject_isolated with clause_width * num_clauses < num_vars, a NULL pointer with
+ * num_problems > 0.
+ * (Additive entry point: msat_version() stays 3, no struct changed.) */
+int msat_pool_generate(int32_t num_problems, int32_t num_vars, int32_t num_clauses, int32_t clause_width,
+                       uint64_t seed, uint64_t counter, int32_t reject_isolated, int32_t max_attempts,
+                       int32_t *clauses, uint8_t *planted, int32_t *attempts, void *stream);
 
 /* Reset the envs with reset_mask[b] != 0 (NULL: all envs).
  * new_problem_idx (B,) and new_assign (B,V) are explicit inputs for exact-parity

@@ -361,6 +361,35 @@ int msat_gather_rows(const int32_t *idx, int32_t S, int32_t nfields, const void 
  * (the batch cannot be indexed in int32; the caller must split it). */
 int msat_graph_bases(int32_t S, const int32_t *inst, const int32_t *nv, const int32_t *nc, const int32_t *ne,
                      int32_t *bases, int32_t *totals, void *stream);
+/* The graph templates of a problem pool on the device: the twelve arrays that learners/graphs.py::build_templates
+ * makes on the host, element for element (the layouts msat_assemble_graph_batch reads).  clauses (N,C,K) int32,
+ * signed and 1-based; literal 0 names no variable and adds no edge (the network's adjacency, not the env's
+ * literal-0 quirk), and so does a literal with |l| > V.  Graph 0 of an instance is all V variables and all C
+ * clauses in order; graph 1 + i is agent i's: its own variables in order (lo = i * (V / A) + min(i, V % A),
+ * V / A + (i < V % A) of them), then its neighbours ascending (the variables of real literals of related clauses
+ * that are not its own), and the related clauses ascending (those with a real literal on an own variable).
+ *   msat_graph_template_counts: gv, gc, ge (N, A+2): the var-row, clause-row and incidence starts of each graph
+ *   within its instance; the last column is the instance total.
+ *   The caller scans the totals over N: voff, coff, eoff (N+1,) and poff = voff + n.
+ *   msat_graph_template_fill: vgid (total var rows), cgid (total clause rows), slots (total clause rows, 3):
+ *   (instance-relative var row << 1) | neg, -1 for literal 0 and the columns past K; ptr (total var rows + N): per
+ *   instance a CSR over all its var rows (rows + 1 entries); inc (total incidences): (instance-relative clause
+ *   row << 1) | neg, per var row in (clause row, slot) order, a variable twice in a clause being two entries.
+ *   total_var_rows / total_clause_rows / total_incidences are voff[N], coff[N], eoff[N].
+ * One workgroup per instance with the instance in LDS: msat_graph_templates_lds_bytes(V, C, K) bytes (0 for
+ * dimensions outside the ranges below); a shape that needs more than 65536 is MSAT_EBADARG (the caller keeps the
+ * host builder for it).  Enqueue only.  N == 0: MSAT_OK without a launch.  MSAT_EBADARG also: N < 0, V outside
+ * [1, 32000], C < 1, K outside [1, 3], A outside [1, V], a NULL pointer with N > 0 (cgid, slots and inc may be NULL
+ * when their total is 0). */
+size_t msat_graph_templates_lds_bytes(int32_t num_vars, int32_t num_clauses, int32_t clause_width);
+int msat_graph_template_counts(const int32_t *clauses, int32_t num_problems, int32_t num_clauses,
+                               int32_t clause_width, int32_t num_vars, int32_t num_agents, int32_t *gv, int32_t *gc,
+                               int32_t *ge, void *stream);
+int msat_graph_template_fill(const int32_t *clauses, int32_t num_problems, int32_t num_clauses, int32_t clause_width,
+                             int32_t num_vars, int32_t num_agents, const int32_t *voff, const int32_t *coff,
+                             const int32_t *eoff, const int32_t *poff, int32_t total_var_rows,
+                             int32_t total_clause_rows, int32_t total_incidences, int32_t *vgid, int32_t *cgid,
+                             int32_t *slots, int32_t *ptr, int32_t *inc, void *stream);
 /* fp64 cycle sums over N transitions (learner:661-719): out[9] = sum reward, sum done, sum solved&done,
  * sum unsat*done, sum episode_step*(solved&done), sum tg, sum tg^2, sum d, sum d^2 (d = tg - vpred). */
 int msat_cycle_metrics(int32_t N, const float *reward, const uint8_t *done, const uint8_t *solved,

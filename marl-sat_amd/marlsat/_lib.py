@@ -93,6 +93,9 @@ def _load():
         "msat_version": (c_int32, []),
         "msat_pool_pack": (c_int32, [P, c_int32, c_int32, c_int32, c_int32, P, P, P]),
         "msat_pool_agent_tables": (c_int32, [POINTER(EnvDesc), P, P, P, P]),
+        "msat_pool_generate": (
+            c_int32, [c_int32, c_int32, c_int32, c_int32, c_uint64, c_uint64, c_int32, c_int32, P, P, P, P]
+        ),
         "msat_env_reset": (
             c_int32, [POINTER(EnvDesc), POINTER(PoolC), POINTER(EnvStateC), P, P, P, c_uint64, c_uint64, P, P]
         ),
@@ -163,6 +166,9 @@ def _load():
     sig["msat_gather_rows"] = (I, [P, I, I, P, P, P, P])
     sig["msat_cycle_metrics"] = (I, [I, P, P, P, P, P, P, P, P, P])
     sig["msat_graph_bases"] = (I, [I, P, P, P, P, P, P, P])
+    sig["msat_graph_templates_lds_bytes"] = (Z, [I, I, I])
+    sig["msat_graph_template_counts"] = (I, [P, I, I, I, I, I, P, P, P, P])
+    sig["msat_graph_template_fill"] = (I, [P, I, I, I, I, I, P, P, P, P, I, I, I, P, P, P, P, P, P])
     sig["msat_gemm_h2_dual"] = (I, [P, I, P, P, P, P, I, I, I, P, I, P, P, P, P, I, I, I, P, I, I, P])
     sig["msat_gemm_wgrad_dual_workspace_bytes"] = (c_size_t, [I, I, I, I, I])
     sig["msat_gemm_wgrad_h2_dual"] = (I, [P, I, P, I, P, I, I, I, I, P, I, P, I, P, I, I, I, I, P, I, I, P, P])
@@ -275,6 +281,9 @@ EXPORTED = (
     "msat_gather_rows",
     "msat_cycle_metrics",
     "msat_graph_bases",
+    "msat_graph_templates_lds_bytes",
+    "msat_graph_template_counts",
+    "msat_graph_template_fill",
     "msat_gemm_h2_dual",
     "msat_gemm_wgrad_dual_workspace_bytes",
     "msat_gemm_wgrad_h2_dual",
@@ -323,6 +332,7 @@ EXPORTED = (
     "msat_version",
     "msat_pool_pack",
     "msat_pool_agent_tables",
+    "msat_pool_generate",
     "msat_env_reset",
     "msat_env_step",
     "msat_env_step_delta",

@@ -94,6 +94,46 @@ class ProblemPool:
             raise ValueError(f"problem pool has a literal with |l| > num_vars={num_vars}")
         self._svf = None
         self._tables = {}  # num_agents -> (rel (N,A,WC), nbr (N,A,WV)) int32 bit words
+        self.planted = None  # generate(): (N,V) uint8, an assignment that satisfies every clause of its instance
+        self.attempts = None  # generate(): (N,) int32, the accepted attempt of each instance
+
+    @classmethod
+    def generate(cls, env_or_shape, num_problems: int, key, *, reject_isolated: bool = True,
+                 max_attempts: int = 64, device=None) -> "ProblemPool":
+        """A pool of planted random k-SAT instances drawn on the device (msat_pool_generate, include/marlsat.h:
+        the reference generator's semantics on Philox words -- the same family of instances as
+        utils/generate_cnf_dataset.py, not the same bytes).  ``env_or_shape``: a SATEnv (its V and C, 3-wide
+        clauses, its device) or (V, C) / (V, C, K).  ``key``: a marlsat.random.Key or an int seed; instance n
+        depends only on (key, n) and the shape.  The pool carries ``planted`` (N,V) uint8 and ``attempts`` (N,)
+        int32.  reject_isolated: redraw an instance that leaves a variable in no clause, up to max_attempts
+        attempts each; an instance that exhausts them raises RuntimeError.  Bad dimensions are the library's
+        MSAT_EBADARG, raised with its message."""
+        if isinstance(env_or_shape, SATEnv):
+            V, C, K = env_or_shape.num_vars, env_or_shape.num_clauses, 3
+            device = env_or_shape.device if device is None else device
+        else:
+            shape = tuple(int(d) for d in env_or_shape)
+            if len(shape) not in (2, 3):
+                raise ValueError(f"generate: shape must be (V, C) or (V, C, K), got {shape}")
+            V, C, K = shape if len(shape) == 3 else shape + (3,)
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        N = int(num_problems)
+        if N < 1:
+            raise ValueError(f"generate: num_problems={N} must be >= 1")
+        k = as_key(key)
+        clauses = torch.empty((N, max(C, 1), max(K, 1)), dtype=torch.int32, device=dev)
+        planted = torch.empty((N, max(V, 1)), dtype=torch.uint8, device=dev)
+        attempts = torch.empty((N,), dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib.msat_pool_generate(N, V, C, K, k.seed, k.counter, int(bool(reject_isolated)),
+                                               int(max_attempts), clauses.data_ptr(), planted.data_ptr(),
+                                               attempts.data_ptr(), _lib.stream_ptr(dev)), "msat_pool_generate")
+        bad = int((attempts < 0).sum().item())
+        if bad:
+            raise RuntimeError(f"generate: {bad} of {N} instances (V={V}, C={C}, K={K}) still had a variable in no "
+                               f"clause after {max_attempts} attempts each; raise max_attempts or the clause count")
+        pool = cls(clauses, V, dev)
+        pool.planted, pool.attempts = planted, attempts
+        return pool
 
     def agent_tables(self, env: "SATEnv"):
         """Per-instance relation / neighbour bit tables for env's agent partition

@@ -26,7 +26,7 @@ import torch
 from .. import _lib
 from ..envs.multi_agent_sat_env import ProblemPool, SATEnv
 from .gnn import GNNActorCritic
-from .graphs import DeviceTemplates, assemble, batch_totals, build_templates
+from .graphs import assemble, batch_totals, make_templates
 from .mappo_gnn_sat_learner import NO_BAD_STEP, activation_plan
 
 L_ = _lib.lib
@@ -34,7 +34,7 @@ L_ = _lib.lib
 
 class BCLearner:
     def __init__(self, config: dict, env: SATEnv, network: GNNActorCritic, pool: ProblemPool,
-                 micro_bytes: Optional[float] = None, actor_only: bool = False):
+                 micro_bytes: Optional[float] = None, actor_only: bool = False, templates: str = "host"):
         if env.action_mode != 0:
             raise ValueError(f"BCLearner: action_mode {env.action_mode} is not supported: the reference's BC labels "
                              f"(compute_joint_labels_parallel_greedy) are mode-0 indices (a local variable or the "
@@ -47,8 +47,8 @@ class BCLearner:
             raise ValueError(f"MINIBATCH_SIZE={self.MB} must be >= 1")
         self.lr = float(config.get("LEARNING_RATE", 3e-4))
         self.A, self.M = env.num_agents, env.max_vars_per_agent
-        self.tpl = DeviceTemplates(build_templates(pool.clauses.cpu().numpy(), env.num_vars, env.num_agents),
-                                   env.num_agents, self.device)
+        # "host": graphs.build_templates + upload; "device": graphs.build_templates_device (the same arrays)
+        self.tpl = make_templates(pool, env.num_vars, env.num_agents, templates, self.device)
         self.actor_only = bool(actor_only)
         rows = self.tpl.mean_actor_rows if self.actor_only else self.tpl.mean_full_rows
         self.micro, _ = activation_plan(config, rows, network.H, network.L, self.MB, 1, micro_bytes)

@@ -13,9 +13,11 @@ sample is encoded as a ragged batch of small graphs:
   graph 0      critic, all V vars and C clauses
   graph 1 + i  agent i, vars = own (in order) ++ neighbours (ascending), clauses = related (ascending)
 
-Templates are built once per (problem pool, agent partition) on the host (static
-data preparation, like packing the pool) and uploaded; per micro-batch a HIP
-kernel instantiates them for the sampled (instance, assignment) pairs.  The
+Templates are built once per (problem pool, agent partition): on the host by
+``build_templates`` (static data preparation, like packing the pool) and uploaded, or
+on the device by ``build_templates_device`` (msat_graph_template_counts / _fill, the
+same twelve arrays element for element; what a run that refreshes its pool uses).  Per
+micro-batch a HIP kernel instantiates them for the sampled (instance, assignment) pairs.  The
 adjacency used here is the network's (``create_static_graph``, literal 0 adds
 nothing), not the env's literal-0 quirk.
 """
@@ -160,6 +162,27 @@ class DeviceTemplates:
         self.mean_full_rows = float((t.gv[:, -1] + t.gc[:, -1]).mean())
         self.mean_actor_rows = float((t.gv[:, -1] - t.gv[:, 1] + t.gc[:, -1] - t.gc[:, 1]).mean())
 
+    @classmethod
+    def from_device(cls, A: int, vgid, cgid, slots, ptr, inc, voff, coff, eoff, poff, gv, gc, ge) -> "DeviceTemplates":
+        """The same object from the twelve arrays already on the device (int32, the layouts of ``Templates``;
+        build_templates_device).  Reads the two small (N, A+2) tables gv and gc once for the row statistics."""
+        self = cls.__new__(cls)
+        self.A, self.G = A, A + 1
+        self.vgid, self.cgid, self.slots, self.ptr, self.inc = vgid, cgid, slots, ptr, inc
+        self.voff, self.coff, self.eoff, self.poff = voff, coff, eoff, poff
+        self.gv, self.gc, self.ge = gv, gc, ge
+        col = lambda t, j: t[:, j].contiguous()
+        self.full_v, self.full_c, self.full_e = col(gv, -1), col(gc, -1), col(ge, -1)
+        self.crit_v, self.crit_c, self.crit_e = col(gv, 1), col(gc, 1), col(ge, 1)
+        self.actor_v = self.full_v - self.crit_v
+        self.actor_c = self.full_c - self.crit_c
+        self.actor_e = self.full_e - self.crit_e
+        hv, hc = torch.stack((gv, gc)).cpu().numpy()  # the same expressions as the host constructor's
+        self.max_full_rows = int((hv[:, -1] + hc[:, -1]).max())
+        self.mean_full_rows = float((hv[:, -1] + hc[:, -1]).mean())
+        self.mean_actor_rows = float((hv[:, -1] - hv[:, 1] + hc[:, -1] - hc[:, 1]).mean())
+        return self
+
     def counts(self, actor_only: bool = False, critic_only: bool = False):
         """Per-instance (var rows, clause rows, incidences) of one sample's graphs."""
         if actor_only:
@@ -167,6 +190,59 @@ class DeviceTemplates:
         if critic_only:
             return self.crit_v, self.crit_c, self.crit_e
         return self.full_v, self.full_c, self.full_e
+
+
+TEMPLATE_LDS_LIMIT = 65536  # msat_graph_template_counts / _fill refuse a shape that needs more (marlsat_net.h)
+
+
+def device_templates_fit(V: int, C: int, K: int) -> bool:
+    """True when the template kernels take the shape: one instance fits their LDS plan."""
+    need = int(_lib.lib.msat_graph_templates_lds_bytes(V, C, K))
+    return 0 < need <= TEMPLATE_LDS_LIMIT
+
+
+def build_templates_device(pool, V: int, A: int) -> DeviceTemplates:
+    """``DeviceTemplates(build_templates(pool.clauses.cpu().numpy(), V, A), A, device)`` without the host loop:
+    a count pass (gv, gc, ge per instance), an exclusive scan over the instances (torch.cumsum in int64, cold),
+    ONE device -> host read of the three totals to size the arrays, and a fill pass.  ``pool``: a ProblemPool
+    (its (N, C, K) int32 ``clauses``).  A shape past the kernels' LDS bound falls back to the host builder (same
+    result); a pool whose rows do not fit int32 indices is refused."""
+    cl = pool.clauses
+    N, C, K = (int(d) for d in cl.shape)
+    dev = cl.device
+    if N == 0 or not device_templates_fit(V, C, K):
+        return DeviceTemplates(build_templates(cl.cpu().numpy(), V, A), A, dev)
+    st = _lib.stream_ptr(dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    gv, gc, ge = i32(N, A + 2), i32(N, A + 2), i32(N, A + 2)
+    _lib.check(_lib.lib.msat_graph_template_counts(cl.data_ptr(), N, C, K, V, A, gv.data_ptr(), gc.data_ptr(),
+                                                   ge.data_ptr(), st), "msat_graph_template_counts")
+    per = torch.stack((gv[:, -1], gc[:, -1], ge[:, -1]), 1).to(torch.int64)
+    off = torch.cat((torch.zeros((1, 3), dtype=torch.int64, device=dev), torch.cumsum(per, 0)))
+    tv, tc, te = (int(v) for v in off[-1].tolist())  # sizes the arrays: the one read
+    if max(tv + N, 3 * tc, te) > 2 ** 31 - 1:
+        raise ValueError(f"graph templates of {N} instances exceed int32 indices (var rows, clause rows, incidences "
+                         f"= {tv}, {tc}, {te}): use a smaller pool")
+    off32 = off.to(torch.int32)
+    voff, coff, eoff = (off32[:, j].contiguous() for j in range(3))
+    poff = voff + torch.arange(N + 1, dtype=torch.int32, device=dev)
+    vgid, cgid, slots, ptr, inc = i32(tv), i32(tc), i32(tc, 3), i32(tv + N), i32(te)
+    _lib.check(_lib.lib.msat_graph_template_fill(
+        cl.data_ptr(), N, C, K, V, A, voff.data_ptr(), coff.data_ptr(), eoff.data_ptr(), poff.data_ptr(), tv, tc, te,
+        vgid.data_ptr(), _lib.ptr(cgid) if tc else None, _lib.ptr(slots) if tc else None, ptr.data_ptr(),
+        _lib.ptr(inc) if te else None, st), "msat_graph_template_fill")
+    return DeviceTemplates.from_device(A, vgid, cgid, slots, ptr, inc, voff, coff, eoff, poff, gv, gc, ge)
+
+
+def make_templates(pool, V: int, A: int, templates: str = "host", device=None) -> DeviceTemplates:
+    """The learners' ``templates=`` switch: "host" (build_templates + upload to ``device``, the default) or
+    "device" (build_templates_device, on the pool's device)."""
+    if templates == "device":
+        return build_templates_device(pool, V, A)
+    if templates != "host":
+        raise ValueError(f"templates must be 'host' or 'device', got {templates!r}")
+    return DeviceTemplates(build_templates(pool.clauses.cpu().numpy(), V, A), A,
+                           device if device is not None else pool.clauses.device)
 
 
 @dataclass

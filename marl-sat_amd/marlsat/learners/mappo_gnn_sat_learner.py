@@ -33,7 +33,7 @@ from ..envs.multi_agent_sat_env import ObsDict, ProblemPool, SATEnv, SATState
 from ..random import Key, as_key, split
 from .collectives import allreduce_grads, allreduce_sums, global_moments, world_size
 from .gnn import GNNActorCritic
-from .graphs import DeviceTemplates, GraphBatch, assemble, batch_totals, build_templates
+from .graphs import GraphBatch, assemble, batch_totals, make_templates
 from .ops import gae as device_gae
 
 L_ = _lib.lib
@@ -153,9 +153,13 @@ class MAPPOLearner:
     """Device implementation of make_train_cycle's _train_cycle (see module docstring)."""
 
     def __init__(self, config: dict, env: SATEnv, network: GNNActorCritic, pool: ProblemPool,
-                 dist=None, micro_bytes: Optional[float] = None):
+                 dist=None, micro_bytes: Optional[float] = None, templates: str = "host"):
+        """templates: "host" builds the graph templates with graphs.build_templates and uploads them; "device"
+        builds them with graphs.build_templates_device (the same arrays; the host builder for a shape past the
+        kernels' LDS bound)."""
         self.cfg = dict(config)
-        self.env, self.net, self.pool = env, network, pool
+        self.env, self.net = env, network
+        self.templates, self.micro_bytes = templates, micro_bytes
         self.dist = dist
         self.world = world_size(dist)
         self.device = env.device
@@ -166,20 +170,38 @@ class MAPPOLearner:
         if N % self.MB:
             raise ValueError(f"NUM_STEPS*NUM_ENVS={N} must be divisible by MINIBATCH_SIZE={self.MB} (learner:582-592)")
         self.n_minibatches = N // self.MB
-        self.tpl = DeviceTemplates(build_templates(pool.clauses.cpu().numpy(), env.num_vars, env.num_agents),
-                                   env.num_agents, self.device)
-        self.micro, self.chunk = activation_plan(config, self.tpl.mean_full_rows, network.H, network.L, self.MB,
-                                                 self.B, micro_bytes)
-        # the inference chunk of an actor-only batch (policy(actor_only=True)): the same budget over fewer rows
-        _, self.actor_chunk = activation_plan(config, self.tpl.mean_actor_rows, network.H, network.L, self.MB,
-                                              self.B, micro_bytes)
+        self.pool = None
+        self.set_pool(pool)
         self.A, self.M = env.num_agents, env.max_vars_per_agent
         self.mode = env.action_mode
-        self.svf = pool.static_var_features()
         # parity instrumentation: a list makes ppo_update record, per Adam step, the minibatch rows,
         # the parameters it started from, the (all-reduced) gradient and the learning rate
         self.trace: Optional[list] = None
         self._alloc()
+
+    def set_pool(self, pool: ProblemPool) -> None:
+        """Train on another pool of the same (V, C, K) from now on: replaces the pool, its graph templates and its
+        static variable features, and plans the micro-batch and the two inference chunks again from the new
+        templates' row counts.  The network, the optimiser state and the rollout buffers stay.  A RunnerState made
+        over the old pool is invalid (its env state names the old pool's instances): call init_runner_state again."""
+        old = self.pool
+        if old is not None and (pool.num_vars, pool.num_clauses, pool.clause_width) != (
+                old.num_vars, old.num_clauses, old.clause_width):
+            raise ValueError(f"set_pool: the new pool is (V, C, K) = ({pool.num_vars}, {pool.num_clauses}, "
+                             f"{pool.clause_width}); the learner's is ({old.num_vars}, {old.num_clauses}, "
+                             f"{old.clause_width})")
+        if pool.num_vars != self.env.num_vars or pool.num_clauses != self.env.num_clauses:
+            raise ValueError(f"pool is V={pool.num_vars}, C={pool.num_clauses}; env is V={self.env.num_vars}, "
+                             f"C={self.env.num_clauses}")
+        net = self.net
+        self.tpl = make_templates(pool, self.env.num_vars, self.env.num_agents, self.templates, self.device)
+        self.micro, self.chunk = activation_plan(self.cfg, self.tpl.mean_full_rows, net.H, net.L, self.MB, self.B,
+                                                 self.micro_bytes)
+        # the inference chunk of an actor-only batch (policy(actor_only=True)): the same budget over fewer rows
+        _, self.actor_chunk = activation_plan(self.cfg, self.tpl.mean_actor_rows, net.H, net.L, self.MB, self.B,
+                                              self.micro_bytes)
+        self.svf = pool.static_var_features()
+        self.pool = pool
 
     def _alloc(self):
         T, B, V, A, M, dev = self.T, self.B, self.env.num_vars, self.A, self.M, self.device

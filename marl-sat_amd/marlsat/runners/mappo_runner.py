@@ -13,6 +13,11 @@ Same config file and keys (MAPPO_CONFIG.yaml), same flow (runner:76-464):
      updates, ``checkpoints/latest_model_0`` rewritten every update;
   5. final greedy evaluation of every eval problem -> ``test_solutions.txt`` (the
      format ``src/test/verify_solutions.py`` parses) and the solve-rate summary.
+``generation.ENABLED=true`` (utils/generation.py): step 1 is replaced by pools drawn on the device
+(``ProblemPool.generate``): an eval pool of NUM_EVAL instances once, written as DIMACS files under
+``<run_dir>/generated_eval/`` so that ``verify_solutions_file`` works on the run, and a train pool of NUM_TRAIN
+instances that is replaced every REFRESH_EVERY updates (``MAPPOLearner.set_pool`` + a fresh runner state; both
+learners build their graph templates on the device).  CNF_DATA_DIR is not read.
 Multi-GPU: launch with torchrun; every rank trains its env shard, gradients are
 all-reduced (learners/collectives.py); rank 0 logs, evaluates and saves.
 
@@ -39,7 +44,10 @@ from ..learners.gnn import GNNActorCritic
 from ..learners.mappo_gnn_sat_learner import MAPPOLearner
 from ..random import Key, PRNGKey, split
 from ..utils import checkpoints as ck
+from ..envs.multi_agent_sat_env import ProblemPool
 from ..utils.data_parser import clauses_array, load_cnf_problems, split_train_eval
+from ..utils.device_generator import write_pool
+from ..utils.generation import eval_pool_key, instance_name, parse_generation, train_pool_key
 from ..utils.generate_cnf_dataset import has_isolated_variable
 
 METRICS_HEADER = ("update,mean_return,solve_rate,avg_unsat_clauses,avg_solve_steps,explained_variance,"
@@ -152,14 +160,21 @@ def run(config: Dict, log=print) -> Dict:
     random.seed(seed)
     np.random.seed(seed)
     key = PRNGKey(seed)
-    problems_raw = load_cnf_problems(config.get("CNF_DATA_DIR", "data"))
-    if not problems_raw:
-        log("no .cnf problems found")
-        return {}
-    tr_idx, ev_idx = split_train_eval(len(problems_raw), seed)
-    train_raw = [problems_raw[i] for i in tr_idx]
-    eval_raw = [problems_raw[i] for i in ev_idx]
-    log(f"[*] {len(problems_raw)} problems: {len(train_raw)} train (80%), {len(eval_raw)} eval (20%)")
+    gen_plan = parse_generation(config)
+    if gen_plan.enabled:
+        problems_raw = train_raw = []
+        log(f"[*] generated pools: {gen_plan.num_train} train instances"
+            f"{f', redrawn every {gen_plan.refresh_every} updates' if gen_plan.refresh_every else ''}, "
+            f"{gen_plan.num_eval} eval instances")
+    else:
+        problems_raw = load_cnf_problems(config.get("CNF_DATA_DIR", "data"))
+        if not problems_raw:
+            log("no .cnf problems found")
+            return {}
+        tr_idx, ev_idx = split_train_eval(len(problems_raw), seed)
+        train_raw = [problems_raw[i] for i in tr_idx]
+        eval_raw = [problems_raw[i] for i in ev_idx]
+        log(f"[*] {len(problems_raw)} problems: {len(train_raw)} train (80%), {len(eval_raw)} eval (20%)")
     fc = flat_config(config)
     rewards = fc.get("rewards") or {}
     env = SATEnv(fc["NUM_VARS"], fc["NUM_CLAUSES"], fc["MAX_STEPS"], vars_per_agent=fc.get("VARS_PER_AGENT"),
@@ -175,8 +190,15 @@ def run(config: Dict, log=print) -> Dict:
             f"{', ...' if len(iso) > 5 else ''}): at zero-initialised biases such a variable is a constant LayerNorm "
             f"row whose gradient overflows fp32 at depth (tests/test_isolated_variable.py); the learner stops with "
             f"FloatingPointError if an update turns non-finite")
-    train_pool = env.make_pool(np.stack([clauses_array(p) for p in train_raw]))
-    eval_pool = env.make_pool(np.stack([clauses_array(p) for p in eval_raw])) if eval_raw else None
+    if gen_plan.enabled:
+        # every rank draws the same pools from the same keys (ranks differ in their reset keys only): no broadcast
+        draw = lambda n, k: ProblemPool.generate(env, n, k, reject_isolated=True, max_attempts=gen_plan.max_attempts)
+        train_pool = draw(gen_plan.num_train, train_pool_key(seed, 0))
+        eval_pool = draw(gen_plan.num_eval, eval_pool_key(seed))
+        eval_raw = [{"name": instance_name(env.num_vars, i)} for i in range(gen_plan.num_eval)]
+    else:
+        train_pool = env.make_pool(np.stack([clauses_array(p) for p in train_raw]))
+        eval_pool = env.make_pool(np.stack([clauses_array(p) for p in eval_raw])) if eval_raw else None
     net = GNNActorCritic(fc["GNN_HIDDEN_DIM"], fc["GNN_NUM_MESSAGE_PASSING_STEPS"], env.num_agents,
                          env.max_vars_per_agent, env.action_mode, env.num_vars, seed=seed)
     anneal = bool(fc.get("ANNEAL_LR", False))
@@ -195,15 +217,19 @@ def run(config: Dict, log=print) -> Dict:
             log("injected BC encoder + actor parameters")
         else:
             log("warning: BC checkpoint not found; training from scratch")
-    learner = MAPPOLearner(fc, env, net, train_pool, dist=dist)
+    tpl_on = "device" if gen_plan.enabled else "host"  # a refreshed pool prepares its templates on the device
+    learner = MAPPOLearner(fc, env, net, train_pool, dist=dist, templates=tpl_on)
     ne = max(1, len(eval_raw))  # evaluation runs every eval problem as one device batch
-    eval_learner = MAPPOLearner(dict(fc, NUM_ENVS=ne, NUM_STEPS=1, MINIBATCH_SIZE=ne), env, net, eval_pool) \
-        if eval_pool is not None else None
+    eval_learner = MAPPOLearner(dict(fc, NUM_ENVS=ne, NUM_STEPS=1, MINIBATCH_SIZE=ne), env, net, eval_pool,
+                                templates=tpl_on) if eval_pool is not None else None
     time_str = datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
     run_dir = os.path.abspath(os.path.join(config.get("SAVE_DIR", "experiments"), time_str))
     ckpt_dir = os.path.join(run_dir, "checkpoints")
     if rank == 0:
         os.makedirs(ckpt_dir, exist_ok=True)
+        if gen_plan.enabled:  # the eval pool as files, named as test_solutions.txt names them
+            names = write_pool(eval_pool, os.path.join(run_dir, "generated_eval"))
+            assert names == [p["name"] for p in eval_raw]
     key, k_rs = split(key, 2)
     rs = learner.init_runner_state(Key(k_rs.seed + rank, k_rs.counter))
     gen = torch.Generator().manual_seed(seed + rank)
@@ -216,6 +242,13 @@ def run(config: Dict, log=print) -> Dict:
         if logf:
             logf.write(METRICS_HEADER)
         for u in range(n_upd):
+            if gen_plan.enabled and gen_plan.refresh_before(u):
+                e = gen_plan.pool_of_update(u)
+                learner.set_pool(ProblemPool.generate(env, gen_plan.num_train, train_pool_key(seed, e),
+                                                      reject_isolated=True, max_attempts=gen_plan.max_attempts))
+                # the old state names the old pool's instances: its unfinished episodes end here and, never
+                # having produced a done, enter no metric
+                rs = learner.init_runner_state(Key(k_rs.seed + rank, k_rs.counter + e))
             rs, m = learner.train_cycle(rs, u, gen)
             last = m
             if rank != 0:
@@ -236,6 +269,9 @@ def run(config: Dict, log=print) -> Dict:
         if logf:
             logf.close()
     result = {"run_dir": run_dir, "train_seconds": time.time() - t0, "last_metrics": last}
+    if gen_plan.enabled:
+        result["generated_eval_dir"] = os.path.join(run_dir, "generated_eval")
+        result["train_pools"] = gen_plan.pool_of_update(n_upd - 1) + 1 if n_upd > 0 else 1
     if rank == 0 and eval_learner is not None:
         st = ck.restore_checkpoint(ckpt_dir, "latest_model_", 0)
         if st is not None:
