@@ -19,7 +19,11 @@ extern "C" {
 #endif
 
 /* C[M,N] (+)= A[M,K] @ op(B) (+ bias[N]); op(B) = B[K,N] (transB=0) or B[N,K]^T (transB=1).
- * Row-major with leading dims; fp32 in / fp32 accumulate on the matrix cores. */
+ * Row-major with leading dims; fp32 in / fp32 accumulate on the matrix cores.
+ * `accumulate` is a flag (here and in every export below): 0 overwrites, any nonzero value adds to
+ * what the output holds.  Only the M x N (K x N for the weight gradients) elements are written; the
+ * ld - N gap of every output row is left as it was, and the ld - K gaps of the inputs are never read.
+ * K = 0 is admitted: C = bias (zero without bias), or C += bias with accumulate. */
 int msat_gemm(const float *A, int32_t lda, const float *B, int32_t ldb, int32_t transB, float *C,
               int32_t ldc, const float *bias, int32_t M, int32_t N, int32_t K, int32_t accumulate,
               void *stream);
@@ -68,14 +72,18 @@ int msat_gemm_h2(const float *A, int32_t lda, const int32_t *rexp, const void *W
                  int32_t accumulate, void *stream);
 
 /* W[K,N] (+)= A[M,K]^T @ G[M,N]: split over M, partial slabs reduced in a fixed order.
- * K <= 8 (feature / degree columns) streams G once instead of running 128-row MFMA tiles. */
+ * K <= 8 (feature / degree columns) streams G once instead of running 128-row MFMA tiles.
+ * M = 0 is admitted by msat_gemm_wgrad, _rot, _h2 and the duals: accumulate = 0 writes zeros to
+ * W[:, :N], accumulate != 0 leaves W unchanged; neither touches the ldw - N gaps. */
 size_t msat_gemm_wgrad_workspace_bytes(int32_t M, int32_t K, int32_t N);
 int msat_gemm_wgrad(const float *A, int32_t lda, const float *G, int32_t ldg, float *W, int32_t ldw,
                     int32_t M, int32_t K, int32_t N, int32_t accumulate, void *workspace, void *stream);
 /* W[:, (n + rot) % N] (+)= (A^T G)[:, n], 0 <= rot < N: the packed GRU backward rows' gate blocks
  * (n | r | z) into a weight stored (r | z | n) in one pass (learner:62-80 update cells' input rows). */
 /* The same in fp16x2 (three fp16 MFMAs per product) for G = a GRU backward's packed rows with their
- * row scale exponents rexp (msat_gru_ln_bwd_g4fe): K > 8, N <= 384, rot % 4 == 0. */
+ * row scale exponents rexp (msat_gru_ln_bwd_g4fe): K > 8, N <= 384, rot % 4 == 0.
+ * A is split as 2^8 a: full accuracy for 2^-15 <= |a| < 2^7; |a| >= 2^7 sends its workgroup to the bf16x3
+ * fixup (correct, slower), and below 2^-15 an element carries an absolute error up to 2^-33. */
 int msat_gemm_wgrad_h2(const float *A, int32_t lda, const float *G, int32_t ldg, const int32_t *rexp, float *W,
                        int32_t ldw, int32_t M, int32_t K, int32_t N, int32_t rot, int32_t accumulate, void *workspace,
                        void *stream);

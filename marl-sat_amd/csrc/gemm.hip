@@ -517,7 +517,11 @@ extern "C" size_t msat_gemm_wgrad_workspace_bytes(int32_t M, int32_t K, int32_t 
     size_t floats = sp * K * N;
     // msat_gemm_wgrad_rot's tiled fallback runs two narrower products (N - rot and rot columns) in the
     // same workspace, and narrower products take more splits: size for the widest need of any width
-    for (int n = 1; n < N; ++n) floats = std::max(floats, (size_t)wgrad_splits(M, K, n) * K * n);
+    // (the streaming K <= 8 form too: fewer column blocks, more row splits)
+    for (int n = 1; n < N; ++n) {
+        const int spn = std::max(wgrad_splits(M, K, n), K <= kSkinnyK && n % 4 == 0 ? skinny_splits(M, n) : 0);
+        floats = std::max(floats, (size_t)spn * K * n);
+    }
     return floats * sizeof(float) + kWgradFlagBytes;  // + the fp16x2 kernel's workgroup flags
 }
 

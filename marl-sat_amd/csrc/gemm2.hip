@@ -230,10 +230,6 @@ gemm2_kernel(const float *__restrict__ A, int lda, const float *__restrict__ B, 
                 if (row >= M) continue;
                 float *c = C + (size_t)row * ldc + col;
                 const float v = acc[i][j][reg] + bv;
-                if (accumulate == 2) {
-                    if (v != v) *c = v;
-                    continue;
-                }
                 *c = accumulate ? *c + v : v;
             }
         }

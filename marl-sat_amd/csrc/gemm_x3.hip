@@ -840,7 +840,8 @@ wgrad_x3_kernel(const float *__restrict__ A, int lda, const float *__restrict__ 
 // fp16x2 kernel: it computes only the workgroups flagged there.
 // NP = 2: fp16x2 (three fp16 MFMAs).  G is scaled by 2^e with e the smallest row exponent of the
 // split (rexp, written by the GRU backward that produced G: every scaled row below 2^15, the
-// largest at full precision) and the partial by 2^-e (exact).  A is range-checked (|a| < 2^15): a
+// largest at full precision), A by 2^kWgA, and the partial by 2^-(e + kWgA) (exact).  A is range-checked
+// (|a| < 2^(15 - kWgA)): a
 // workgroup that loads anything outside sets flags[id] and stores nothing; G needs no check (a
 // non-finite G row stays non-finite through the fp16 products, as it would in fp32).
 //
@@ -850,6 +851,13 @@ wgrad_x3_kernel(const float *__restrict__ A, int lda, const float *__restrict__ 
 
 constexpr int kWWT = 512;
 constexpr int kWWN = 384;  // widest N
+// fp16x2 form: A is split as 2^kWgA a (the fp32-row counterpart of the planes form's kPlA below).  The lo half
+// of an fp16 pair lands on fp16's subnormal grid (spacing 2^-24) once |x| < 2^-3, an absolute error up to 2^-25
+// per element; unscaled, that is over 4e-6 |a| for every |a| < 2^-7, which a one-row product shows in full
+// (tests/test_gemm_placement_gpu.py, M = 1: 1.015 of the bound at |a| = 0.0059).  2^8 moves that to
+// |a| < 2^-15.  The price: the range check flags |a| >= 2^(15 - kWgA) = 128 (a flagged workgroup is recomputed
+// in bf16x3, correct either way).
+constexpr int kWgA = 8;
 
 typedef unsigned short WwLds[2][12][kW3Plane];  // [buf][A planes | G planes]: 96 KiB
 
@@ -955,7 +963,8 @@ __device__ __forceinline__ void wgrad_w_body(const float *__restrict__ A, int ld
             }
         } else {
             amax = fmaxf(amax, fmaxf(fmaxf(fabsf(r.a.x), fabsf(r.a.y)), fmaxf(fabsf(r.a.z), fabsf(r.a.w))));
-            const SplitH4 xa = splith4(r.a);
+            constexpr float as = (float)(1 << kWgA);
+            const SplitH4 xa = splith4(make_float4(r.a.x * as, r.a.y * as, r.a.z * as, r.a.w * as));
             put(buf, 0, xa.p[0]);
             put(buf, 1, xa.p[1]);
 #pragma unroll
@@ -1049,7 +1058,7 @@ __device__ __forceinline__ void wgrad_w_body(const float *__restrict__ A, int ld
             if (s + k < ns) iter(s + k, R[(k + 1) % NPF], R[k]);
     }
     if constexpr (NP == 2) {
-        const int bad = __syncthreads_or(!(amax < 32768.0f));
+        const int bad = __syncthreads_or(!(amax < 32768.0f / (1 << kWgA)));
         if (t == 0) *flag = bad;
         if (bad) return;
     }
@@ -1064,7 +1073,7 @@ __device__ __forceinline__ void wgrad_w_body(const float *__restrict__ A, int ld
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const int row = k0 + wk + 32 * i + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-                if (row < K) P[(size_t)row * N + oc] = NP == 2 ? ldexpf(acc[i][j][reg], -ge) : acc[i][j][reg];
+                if (row < K) P[(size_t)row * N + oc] = NP == 2 ? ldexpf(acc[i][j][reg], -ge - kWgA) : acc[i][j][reg];
             }
         }
 }
