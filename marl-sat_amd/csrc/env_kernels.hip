@@ -195,6 +195,18 @@ __device__ __forceinline__ void load_x_bits(const EnvParams &p, const EnvLds &l,
 constexpr int kPfClause = 4;
 constexpr int kPfRel = 4;
 constexpr int kPfNbr = 2;
+// The depths of one instantiation.  The kernels of a launch with an obs shadow and int32 observations (SCATTER)
+// prefetch no rel word: their running step scatters its changed elements and reads none, and their full writes load
+// the table where they stage it (four loads per lane less on the step's chain).  Every other kernel keeps the depths
+// above.  (Depths by width -- the whole uf200 row in registers at 64 and 128 lanes, 14 + 4 and 7 + 2 words -- did not
+// make a narrow width win: DESIGN.md section 10, round 15.)
+template <bool SCATTER>
+struct PfDepth {
+    static constexpr int clause = kPfClause;
+    static constexpr int nbr = kPfNbr;
+    static constexpr int rel = SCATTER ? 1 : kPfRel;  // (SCATTER: one unused word, not loaded)
+    static constexpr bool load_rel = !SCATTER;
+};
 
 // Every global load this wave has issued has landed behind this point, and the compiler's wait-count bookkeeping knows
 // it (an s_waitcnt in inline asm is opaque to it).  gfx950 counts loads and stores in the one vmcnt, so a register
@@ -234,11 +246,12 @@ __device__ __forceinline__ void clause_slice(const EnvParams &p, const EnvLds &l
 
 // Evaluate every clause of pool row `pidx` against l.x: clause bits -> l.sat,
 // bytes -> sat_g / ntrue_g, unsat count (and PBRS newly-satisfied) -> red[0] / red[1].
-// The first NPF slices use the lane's prefetched pool words pw[].
-template <int T, bool kPbrs, int NPF>
+// The first NPF slices (all NC of the prefetch, or none) use the lane's prefetched pool words pw[].
+template <int T, bool kPbrs, bool kPf, int NC>
 __device__ __forceinline__ void eval_clauses(const EnvParams &p, const EnvLds &l, const uint16_t *__restrict__ lits,
                                              int pidx, uint8_t *__restrict__ sat_g, uint8_t *__restrict__ ntrue_g,
-                                             const uint64_t (&pw)[kPfClause]) {
+                                             const uint64_t (&pw)[NC]) {
+    constexpr int NPF = kPf ? NC : 0;
     const uint64_t *prow = reinterpret_cast<const uint64_t *>(lits) + (size_t)pidx * p.C;
     const int lane = threadIdx.x & 63;
     int unsat = 0, newly = 0;  // wave-uniform
@@ -589,18 +602,18 @@ __device__ __forceinline__ void scatter_clause(const EnvParams &p, const EnvLds 
 //                   prefetch (pnbr[j] is nbr word tid + j T of the instance) or, past it, from the pool's row.
 // l.own (agent_of_var, 16 bits per variable) was filled before the first barrier of the step.  The bits of l.x, l.sx
 // and the nbr words past V are zero or meet a zero nbr bit.
-template <int T>
+template <int T, int NC, int NN>
 __device__ __forceinline__ void scatter_obs(const EnvParams &p, const EnvLds &l, const msat_pool &pool, int pidx,
-                                            const uint64_t (&pw)[kPfClause], const uint32_t (&pnbr)[kPfNbr],
+                                            const uint64_t (&pw)[NC], const uint32_t (&pnbr)[NN],
                                             int32_t *__restrict__ o) {
     const int tid = threadIdx.x;
     const uint64_t *prow = reinterpret_cast<const uint64_t *>(pool.lits) + (size_t)pidx * p.C;
 #pragma unroll
-    for (int j = 0; j < kPfClause; ++j) {
+    for (int j = 0; j < NC; ++j) {
         const int c = tid + j * T;
         if (c < p.C) scatter_clause(p, l, c, pw[j], o);
     }
-    for (int c = tid + kPfClause * T; c < p.C; c += T) {
+    for (int c = tid + NC * T; c < p.C; c += T) {
         const uint64_t w = prow[c];
         retire_loads();
         scatter_clause(p, l, c, w, o);
@@ -630,8 +643,8 @@ __device__ __forceinline__ void scatter_obs(const EnvParams &p, const EnvLds &l,
         task_advance(ti, stride, p.WV);
     };
 #pragma unroll
-    for (int j = 0; j < kPfNbr; ++j) task(pnbr[j]);  // (zero past the table's end)
-    for (int t = tid + kPfNbr * T; t < ntask; t += T) {
+    for (int j = 0; j < NN; ++j) task(pnbr[j]);  // (zero past the table's end)
+    for (int t = tid + NN * T; t < ntask; t += T) {
         const uint32_t m = nbr_g[t];
         retire_loads();
         task(m);
@@ -639,10 +652,9 @@ __device__ __forceinline__ void scatter_obs(const EnvParams &p, const EnvLds &l,
 }
 
 // The prefetch of an instance's pool row and agent tables into this lane's registers (one round trip).
-template <int T>
-__device__ __forceinline__ void prefetch_instance(const EnvParams &p, const msat_pool &pool, int n,
-                                                  uint64_t (&w)[kPfClause], uint32_t (&rl)[kPfRel],
-                                                  uint32_t (&nb)[kPfNbr]) {
+template <int T, bool kRel, int NC, int NR, int NN>
+__device__ __forceinline__ void prefetch_instance(const EnvParams &p, const msat_pool &pool, int n, uint64_t (&w)[NC],
+                                                  uint32_t (&rl)[NR], uint32_t (&nb)[NN]) {
     // Branch-free: every lane loads a clamped (valid) address and zeroes what lies past the end.  Loads under a
     // branch leave the compiler's vmcnt bookkeeping unsure how many are in flight, so the first use of an
     // EARLIER load (the assignment byte) then waited for all of these (a whole round trip before the flips).
@@ -652,19 +664,23 @@ __device__ __forceinline__ void prefetch_instance(const EnvParams &p, const msat
     const uint32_t *nbr_g = pool.nbr + (size_t)n * p.A * p.WV;
     const int nrel = p.A * p.WC, nnbr = p.A * p.WV;
 #pragma unroll
-    for (int j = 0; j < kPfClause; ++j) {
+    for (int j = 0; j < NC; ++j) {
         const int c = tid + j * T;
         const uint64_t v = prow[min(c, p.C - 1)];
         w[j] = c < p.C ? v : 0ull;
     }
 #pragma unroll
-    for (int j = 0; j < kPfRel; ++j) {
+    for (int j = 0; j < NR; ++j) {
+        if (!kRel) {
+            rl[j] = 0u;
+            continue;
+        }
         const int t = tid + j * T;
         const uint32_t v = rel_g[min(t, nrel - 1)];
         rl[j] = t < nrel ? v : 0u;
     }
 #pragma unroll
-    for (int j = 0; j < kPfNbr; ++j) {
+    for (int j = 0; j < NN; ++j) {
         const int t = tid + j * T;
         const uint32_t v = nbr_g[min(t, nnbr - 1)];
         nb[j] = t < nnbr ? v : 0u;
@@ -705,10 +721,10 @@ __device__ __forceinline__ void reset_assignment(const EnvParams &p, const EnvLd
 // changed straight from the source diff: int32 observations element by element with nothing staged (scatter_obs),
 // int8 ones the dirty chunks behind the staging (write_obs_sparse16).
 // SH: the launch has an obs shadow (shadow::env_kernel; without one the code is the plain full write).
-template <typename ObsT, int T, bool SH>
+template <typename ObsT, int T, bool SH, int NC, int NR, int NN>
 __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const EnvLds &l, const msat_pool &pool,
-                                                    int pidx, bool pf, const uint64_t (&pw)[kPfClause],
-                                                    const uint32_t (&prel)[kPfRel], const uint32_t (&pnbr)[kPfNbr],
+                                                    int pidx, bool pf, const uint64_t (&pw)[NC],
+                                                    const uint32_t (&prel)[NR], const uint32_t (&pnbr)[NN],
                                                     ObsT *__restrict__ o, const ClockStamp *cs,
                                                     uint32_t *__restrict__ srow, bool delta, int delta_g, int ndiff) {
     // srow: the env's obs shadow row (NULL: none), rewritten to describe this write.  delta: l.sx / l.ssat hold the
@@ -735,16 +751,14 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
             scatter_obs<T>(p, l, pool, pidx, pw, pnbr, reinterpret_cast<int32_t *>(o));
             if (cs) cs->mark(4);
 #ifdef MSAT_DEBUG
-            // every element whose value did not change is read back; the evaluator needs the tables in LDS
+            // every element whose value did not change is read back, the evaluator on the instance's table rows in
+            // global memory (a sparse int32 step stages no table in LDS)
             const uint32_t *rel_g = pool.rel + (size_t)pidx * p.A * p.WC;
             const uint32_t *nbr_g = pool.nbr + (size_t)pidx * p.A * p.WV;
-            for (int t = tid; t < p.A * p.WC; t += T) l.rel[t] = rel_g[t];
-            for (int t = tid; t < p.A * p.WV; t += T) l.nbr[t] = nbr_g[t];
-            barrier_lds();
             const ObsGeom g = obs_geom(p);
             for (int e = tid; e < p.A * p.D; e += T) {
-                const int nv = obs_elem(g, l.x, l.sat, l.rel, l.nbr, e);
-                if (nv == obs_elem(g, l.sx, l.ssat, l.rel, l.nbr, e)) MSAT_DCHECK((int)o[e] == nv ? 0 : -1 - e, 1);
+                const int nv = obs_elem(g, l.x, l.sat, rel_g, nbr_g, e);
+                if (nv == obs_elem(g, l.sx, l.ssat, rel_g, nbr_g, e)) MSAT_DCHECK((int)o[e] == nv ? 0 : -1 - e, 1);
             }
 #endif
             return;
@@ -755,14 +769,16 @@ __device__ __forceinline__ void stage_and_write_obs(const EnvParams &p, const En
         const uint32_t *nbr_g = pool.nbr + (size_t)pidx * p.A * p.WV;
         int t0r = 0, t0n = 0;
         if (pf) {
+            if (!kScatter) {  // (the kScatter kernels prefetch no rel word: PfDepth)
 #pragma unroll
-            for (int j = 0; j < kPfRel; ++j)
-                if (tid + j * T < p.A * p.WC) l.rel[tid + j * T] = prel[j];
+                for (int j = 0; j < NR; ++j)
+                    if (tid + j * T < p.A * p.WC) l.rel[tid + j * T] = prel[j];
+                t0r = NR * T;
+            }
 #pragma unroll
-            for (int j = 0; j < kPfNbr; ++j)
+            for (int j = 0; j < NN; ++j)
                 if (tid + j * T < p.A * p.WV) l.nbr[tid + j * T] = pnbr[j];
-            t0r = kPfRel * T;
-            t0n = kPfNbr * T;
+            t0n = NN * T;
         }
         for (int t = t0r + tid; t < p.A * p.WC; t += T) l.rel[t] = rel_g[t];
         for (int t = t0n + tid; t < p.A * p.WV; t += T) l.nbr[t] = nbr_g[t];
@@ -872,11 +888,12 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
         if (MODE == kModeStep || MODE == kModeStepAutoReset)
             MSAT_DCHECK((long long)(b + 1) * p.A * (p.action_mode == 0 ? 1 : p.M) - 1, p.dbg_actions);
     }
-    uint64_t pw[kPfClause];
-    uint32_t prel[kPfRel], pnbr[kPfNbr];
+    using Pf = PfDepth<SH && sizeof(ObsT) == 4>;
+    uint64_t pw[Pf::clause];
+    uint32_t prel[Pf::rel], pnbr[Pf::nbr];
     if (MODE != kModeReset) {
         // ---- then the loads that do: the instance's pool row and agent tables (second round trip) --------
-        prefetch_instance<T>(p, pool, pidx, pw, prel, pnbr);
+        prefetch_instance<T, Pf::load_rel>(p, pool, pidx, pw, prel, pnbr);
         __builtin_amdgcn_sched_barrier(0);
         // a step that may scatter its changed elements (int32, 16-byte groups): the variables' owners, one division
         // per lane while the prefetch is in flight; read behind the clause scan's barrier
@@ -949,9 +966,9 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
         uint8_t *const scan_sat = covered ? nullptr : sat_g;
         uint8_t *const scan_ntrue = covered ? nullptr : ntrue_g;
         if (MODE != kModeObs && p.reward_mode == MSAT_REWARD_PBRS)
-            eval_clauses<T, true, kPfClause>(p, l, pool.lits, pidx, scan_sat, scan_ntrue, pw);
+            eval_clauses<T, true, true>(p, l, pool.lits, pidx, scan_sat, scan_ntrue, pw);
         else
-            eval_clauses<T, false, kPfClause>(p, l, pool.lits, pidx, scan_sat, scan_ntrue, pw);
+            eval_clauses<T, false, true>(p, l, pool.lits, pidx, scan_sat, scan_ntrue, pw);
         barrier_lds();
         cs.mark(2);
         // ---- the decision, taken by every wave for itself from what the scan's barrier published (red[0], red[3])
@@ -1034,7 +1051,7 @@ __device__ __forceinline__ void env_run(const EnvParams &p, const msat_pool &poo
         }
         if (tid < 2) l.red[tid] = 0;  // (every wave has read them: the barrier above)
         barrier_lds();
-        eval_clauses<T, false, 0>(p, l, pool.lits, pidx, sat_g, ntrue_g, pw);
+        eval_clauses<T, false, false>(p, l, pool.lits, pidx, sat_g, ntrue_g, pw);
         barrier_lds();
         if (tid == 0) {
             st.num_unsat[b] = l.red[0];
@@ -1078,14 +1095,15 @@ __device__ __forceinline__ void env_side_reset(const EnvParams &p, const msat_po
     if (b < 0) return;  // fewer than j + 1 envs time out in this launch
     const int pidx = reset_instance(p, new_pidx, seed, ctr, b);
     if (MSAT_DEBUG_BUILD && tid == 0) MSAT_DCHECK(pidx, p.N);
-    uint64_t pw[kPfClause];
-    uint32_t prel[kPfRel], pnbr[kPfNbr];
-    prefetch_instance<T>(p, pool, pidx, pw, prel, pnbr);
+    using Pf = PfDepth<SH && sizeof(ObsT) == 4>;
+    uint64_t pw[Pf::clause];
+    uint32_t prel[Pf::rel], pnbr[Pf::nbr];
+    prefetch_instance<T, Pf::load_rel>(p, pool, pidx, pw, prel, pnbr);
     reset_assignment<T>(p, l, new_assign, seed, ctr, b);
     barrier_lds();
     uint8_t *__restrict__ sat_g = st.clause_sat + (size_t)b * p.C;
     uint8_t *__restrict__ ntrue_g = st.clause_ntrue ? st.clause_ntrue + (size_t)b * p.C : nullptr;
-    eval_clauses<T, false, kPfClause>(p, l, pool.lits, pidx, sat_g, ntrue_g, pw);
+    eval_clauses<T, false, true>(p, l, pool.lits, pidx, sat_g, ntrue_g, pw);
     barrier_lds();
     if (tid == 0) st.num_unsat[b] = l.red[0];
     if ((p.ablate & 3) == 2 || obs == nullptr) return;
