@@ -184,6 +184,9 @@ int msat_gru_ln_bwd(const float *dy, int32_t ldy, const float *Gi, int32_t ldi, 
  * (segment widths multiples of 4, 16-byte aligned rows; w1/w2 may be 0), Wi (Kx, 3H),
  * Wh (H, 3H), bi/bh (3H), out = LN(GRU(hprev, x)).  g4 (nullable, ldg >= 4H) receives the
  * pre-activations [r_pre | z_pre | gin | ghn] for msat_gru_ln_bwd_g4.
+ * Placement: segments, hprev, wi and wh 16-byte aligned with ld % 4 == 0 (segment ld >= width, ldp >= H);
+ * out, g4, bi, bh, ln_scale and ln_bias at any float address, ldo >= H and ldg >= 4H of any value.
+ * Nothing outside the R rows and the named columns of an operand is read into a result or written.
  * Replaces the two gate GEMMs + msat_gru_ln_fwd of update_c / update_v_pos / update_v_neg
  * + LayerNorm_k (learner:68-80). */
 int msat_gru_ln_fused_fwd(const float *x0, int32_t ld0, int32_t w0, const float *x1, int32_t ld1, int32_t w1,
@@ -193,7 +196,8 @@ int msat_gru_ln_fused_fwd(const float *x0, int32_t ld0, int32_t w0, const float 
                           int32_t ldg, int32_t R, int32_t H, void *stream);
 /* Same cell on the bf16 matrix cores (exact bf16x3 split, fp32-accurate; H = 128; register-A on
  * 16x16x32 bf16 MFMAs: activations read straight into registers, only the weights staged): weights given as msat_split_bf16x3_t planes of Wi^T zero-padded
- * to kxp columns (kxp >= Kx, multiple of 32) and of Wh^T (kxp = H).  g4 rows 16-byte aligned. */
+ * to kxp columns (kxp >= Kx, multiple of 32) and of Wh^T (kxp = H).  out and g4 rows 16-byte aligned
+ * (pointer and ldo / ldg % 4 == 0); bi, bh, ln_scale, ln_bias at any float address. */
 int msat_gru_ln_fused_fwd_x3r(const float *x0, int32_t ld0, int32_t w0, const float *x1, int32_t ld1, int32_t w1,
                               const float *x2, int32_t ld2, int32_t w2, const float *hprev, int32_t ldp,
                               const void *wiT_planes, int32_t kxp, const float *bi, const void *whT_planes,

@@ -51,25 +51,27 @@ class Operand:
     check: Callable[[], None]
 
 
-def _fill_pattern(torch, n, kind, dtype):
+def _fill_pattern(torch, n, kind, dtype, fill=None):
     if dtype == torch.int32:
         return torch.full((n,), REXP_POISON, dtype=torch.int32, device="cuda")
     if kind == "in":
-        return torch.full((n,), float("nan"), dtype=torch.float32, device="cuda")
+        return torch.full((n,), float("nan") if fill is None else fill, dtype=torch.float32, device="cuda")
     return torch.full((n,), CANARY, dtype=torch.int32, device="cuda").view(torch.float32)
 
 
-def operand(data, place: Placement = P0, kind: str = "in", min_ld: Optional[int] = None) -> Operand:
+def operand(data, place: Placement = P0, kind: str = "in", min_ld: Optional[int] = None,
+            fill: Optional[float] = None) -> Operand:
     """Place the (rows, cols) tensor `data` at `place` inside a larger buffer: GUARD_ROWS rows of ld elements
-    before and after it and the ld - cols gap in every row, NaN (kind 'in') or the canary pattern (kind
-    'out').  check() asserts everything outside the view bit-identical to what it was when built."""
+    before and after it and the ld - cols gap in every row, NaN (kind 'in'; `fill` puts a finite value there
+    instead) or the canary pattern (kind 'out').  check() asserts everything outside the view bit-identical
+    to what it was when built."""
     import torch
 
     rows, cols = data.shape
     ld = (cols if min_ld is None else min_ld) + place.pad
     assert ld >= cols and data.dtype in (torch.float32, torch.int32)
     n = place.off + (2 * GUARD_ROWS + max(rows, 1)) * ld + 4
-    buf = _fill_pattern(torch, n, kind, data.dtype)
+    buf = _fill_pattern(torch, n, kind, data.dtype, fill)
     assert buf.data_ptr() % 16 == 0
     start = place.off + GUARD_ROWS * ld  # GUARD_ROWS * ld * 4 bytes is a multiple of 16: alignment = off's
     view = buf.as_strided((rows, cols), (ld, 1), start)
@@ -85,9 +87,9 @@ def operand(data, place: Placement = P0, kind: str = "in", min_ld: Optional[int]
     return Operand(buf, view, buf.data_ptr() + 4 * start, ld, check)
 
 
-def vector(data, off: int = 0, kind: str = "in") -> Operand:
+def vector(data, off: int = 0, kind: str = "in", fill: Optional[float] = None) -> Operand:
     """A 1-D operand (bias, colsum output, row exponents) with GUARD_ROWS * len guard entries either side."""
-    op = operand(data.view(1, -1), Placement(off, 0), kind)
+    op = operand(data.view(1, -1), Placement(off, 0), kind, fill=fill)
     op.view = op.view.view(-1)
     return op
 

@@ -10,19 +10,9 @@ gradients 1e-4 of the tensor's max magnitude."""
 import pytest
 import torch
 
+from gru_placement import _ref_gru_ln, build_planes
+
 pytestmark = pytest.mark.gpu
-
-
-def _ref_gru_ln(x, h, wi, bi, wh, bh, sc, lb, H):
-    gi = x @ wi + bi
-    gh = h @ wh + bh
-    r = torch.sigmoid(gi[:, :H] + gh[:, :H])
-    z = torch.sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
-    n = torch.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
-    hn = (1 - z) * n + z * h
-    mean = hn.mean(-1, keepdim=True)
-    var = (hn * hn).mean(-1, keepdim=True) - mean * mean
-    return (hn - mean) * torch.rsqrt(var + 1e-6) * sc + lb, gi, gh
 
 
 def _setup(R, H, kind, seed):
@@ -69,42 +59,24 @@ def _fwd(segs, h, wi, bi, wh, bh, sc, lb, R, H, g4, layout="plain"):
     for t, off, ld, w in segs + [(None, 0, 0, 0)] * (3 - len(segs)):
         args += [t.data_ptr() + 4 * off if t is not None else 0, ld, w]
     if layout == "x3r":  # register-A bf16x3 kernel (16x16x32): transposed planes W^T, K padded to 32
-        K = wi.shape[0]
-        kxp = (K + 31) // 32 * 32
-        pi = torch.empty(3 * 3 * H * kxp + 8, dtype=torch.int16, device="cuda")
-        ph = torch.empty(3 * 3 * H * H + 8, dtype=torch.int16, device="cuda")
-        s = _lib.stream_ptr()
-        _lib.check(_lib.lib.msat_split_bf16x3_t(wi.data_ptr(), K, 3 * H, 3 * H, kxp, pi.data_ptr(), s), "split_t")
-        _lib.check(_lib.lib.msat_split_bf16x3_t(wh.data_ptr(), H, 3 * H, 3 * H, H, ph.data_ptr(), s), "split_t")
-        _lib.check(_lib.lib.msat_gru_ln_fused_fwd_x3r(*args, h.data_ptr(), H, pi.data_ptr(), kxp, bi.data_ptr(),
-                                                      ph.data_ptr(), bh.data_ptr(), sc.data_ptr(), lb.data_ptr(),
+        p = build_planes(wi, wh, H, layout)
+        _lib.check(_lib.lib.msat_gru_ln_fused_fwd_x3r(*args, h.data_ptr(), H, p.pi.data_ptr(), p.kxp, bi.data_ptr(),
+                                                      p.ph.data_ptr(), bh.data_ptr(), sc.data_ptr(), lb.data_ptr(),
                                                       out.data_ptr(), H, g4.data_ptr() if g4 is not None else 0,
-                                                      4 * H, R, H, s), "gru_ln_fused_fwd_x3r")
+                                                      4 * H, R, H, _lib.stream_ptr()), "gru_ln_fused_fwd_x3r")
         torch.cuda.synchronize()
         return out
     if layout == "h2r":  # register-A fp16x2 kernel + bf16x3 fixup of out-of-range tiles
-        K = wi.shape[0]
-        kxp = (K + 31) // 32 * 32
-        s = _lib.stream_ptr()
-        pi = torch.empty(3 * 3 * H * kxp + 8, dtype=torch.int16, device="cuda")
-        ph = torch.empty(3 * 3 * H * H + 8, dtype=torch.int16, device="cuda")
-        qi = torch.empty(2 * 3 * H * kxp + 8, dtype=torch.int16, device="cuda")
-        qh = torch.empty(2 * 3 * H * H + 8, dtype=torch.int16, device="cuda")
-        bad = torch.full((2,), 7, dtype=torch.int32, device="cuda")
+        p = build_planes(wi, wh, H, layout)
         flags = torch.full(((R + 127) // 128 + 1,), 7, dtype=torch.int32, device="cuda")
-        _lib.check(_lib.lib.msat_split_bf16x3_t(wi.data_ptr(), K, 3 * H, 3 * H, kxp, pi.data_ptr(), s), "split_t")
-        _lib.check(_lib.lib.msat_split_bf16x3_t(wh.data_ptr(), H, 3 * H, 3 * H, H, ph.data_ptr(), s), "split_t")
-        _lib.check(_lib.lib.msat_split_f16x2_t(wi.data_ptr(), K, 3 * H, 3 * H, kxp, qi.data_ptr(), bad.data_ptr(), s),
-                   "split_f16x2_t")
-        _lib.check(_lib.lib.msat_split_f16x2_t(wh.data_ptr(), H, 3 * H, 3 * H, H, qh.data_ptr(), bad.data_ptr() + 4,
-                                                s), "split_f16x2_t")
-        _lib.check(_lib.lib.msat_gru_ln_fused_fwd_h2r(*args, h.data_ptr(), H, qi.data_ptr(), qh.data_ptr(),
-                                                      pi.data_ptr(), ph.data_ptr(), kxp, bi.data_ptr(), bh.data_ptr(),
-                                                      sc.data_ptr(), lb.data_ptr(), out.data_ptr(), H,
+        _lib.check(_lib.lib.msat_gru_ln_fused_fwd_h2r(*args, h.data_ptr(), H, p.qi.data_ptr(), p.qh.data_ptr(),
+                                                      p.pi.data_ptr(), p.ph.data_ptr(), p.kxp, bi.data_ptr(),
+                                                      bh.data_ptr(), sc.data_ptr(), lb.data_ptr(), out.data_ptr(), H,
                                                       g4.data_ptr() if g4 is not None else 0, 4 * H, R, H,
-                                                      flags.data_ptr(), bad.data_ptr(), s), "gru_ln_fused_fwd_h2r")
+                                                      flags.data_ptr(), p.bad.data_ptr(), _lib.stream_ptr()),
+                   "gru_ln_fused_fwd_h2r")
         torch.cuda.synchronize()
-        _fwd.last_flags = (flags[:(R + 127) // 128].cpu(), bad.cpu())
+        _fwd.last_flags = (flags[:(R + 127) // 128].cpu(), p.bad.cpu())
         return out
     _lib.check(_lib.lib.msat_gru_ln_fused_fwd(*args, h.data_ptr(), H, wi.data_ptr(), bi.data_ptr(), wh.data_ptr(),
                                               bh.data_ptr(), sc.data_ptr(), lb.data_ptr(), out.data_ptr(), H,
