@@ -408,6 +408,49 @@ int msat_cycle_metrics(int32_t N, const float *reward, const uint8_t *done, cons
                        const int32_t *num_unsatisfied, const int32_t *episode_step, const float *targets,
                        const float *vpred, double *out, void *stream);
 
+/* ---- single-agent PPO baseline (src/learners/single_rl_learner.py, src/runners/single_rl_runner.py) ----
+ * Additive entry points: msat_version() stays 3, no struct changed.  All enqueue only. */
+/* The single-agent PPO loss and its gradient (single_rl_learner.py:118-158) from the network's outputs.
+ * logits (S, V), all finite; action (S) int32; old_logp, adv_n (the minibatch-normalised advantage), value,
+ * targets (S).  Per row, p = softmax(logits): lp = log p[a]; ratio = exp(lp - old_logp); actor =
+ * -min(ratio * adv_n, clip(ratio, 1 - clip_eps, 1 + clip_eps) * adv_n); vl = (value - target)^2 (no 0.5, no value
+ * clipping: the reference's clipped form is commented out); ent = -sum p log p.  total = mean(actor) +
+ * vf_coef * mean(vl) - ent_coef * mean(ent), the means dividing by `minibatch` (as msat_ppo_loss: micro-batch
+ * gradients add up to the minibatch's).  dlogits (S, V) and dvalue (S) are d total; row_terms (S, 3) holds
+ * (actor, vl, ent) per row; sums[0..3] += (sum actor, sum vl, sum ent, invalid rows) in fp64, fixed order.
+ * Ties of the minimum and the clip edges follow msat_ppo_loss (jnp.minimum / jnp.clip: 0.5 / 0.5); inside the
+ * clip interval both branches are the same function and the gradient is the full one.  A row whose action is
+ * outside [0, V) is invalid: its dlogits row, dvalue and row terms are 0 and nothing else of the row is read.
+ * The row's softmax, entropy and ratio are evaluated in fp64 and every output is rounded to fp32 once.
+ * S < 0, V < 1, minibatch < 1, clip_eps <= 0 or not finite, or a NULL pointer with S > 0: MSAT_EBADARG.
+ * S == 0: MSAT_OK without a launch. */
+int msat_ppo_single_loss(const float *logits, int32_t S, int32_t V, const int32_t *action, const float *old_logp,
+                         const float *adv_n, const float *value, const float *targets, float clip_eps,
+                         float ent_coef, float vf_coef, int32_t minibatch, float *dlogits, float *dvalue,
+                         float *row_terms, double *sums, void *stream);
+/* Population standardisation of a minibatch's advantages (single_rl_learner.py:142): x = (x - mean) /
+ * (std + 1e-8) with mean = moments2[0] / n and std = sqrt(max(moments2[1] / n - mean^2, 0)) (ddof 0), moments2
+ * being msat_moments' device output (sum x, sum x^2) for the same x: nothing is read back to the host.  fp64 per
+ * element, rounded once; a constant vector becomes all zeros.  n == 0: MSAT_OK without a launch; a NULL pointer
+ * with n > 0: MSAT_EBADARG. */
+int msat_standardize_pop(float *x, size_t n, const double *moments2, void *stream);
+/* optax.clip_by_global_norm (single_rl_learner.py:52-60) on the flat gradient: norm = sqrt(sum g^2) in fp64 (two
+ * stages, fixed order); norm < max_norm leaves the gradient untouched bitwise, otherwise g *= (float)(max_norm /
+ * norm).  *norm_out (device float) receives the norm before the clip.  A NaN gradient element gives a NaN norm and
+ * NaN gradients (msat_adam_checked's guard then reports the step); nothing is masked.  workspace: at least
+ * msat_clip_global_norm_workspace_doubles(n) doubles.  Two launches, no host read.  n == 0: MSAT_OK without a launch
+ * (*norm_out is left as it was); max_norm <= 0, NaN or inf, a NULL workspace / norm_out, or NULL grads with n > 0:
+ * MSAT_EBADARG. */
+size_t msat_clip_global_norm_workspace_doubles(size_t n);
+int msat_clip_global_norm(float *grads, size_t n, float max_norm, double *workspace, float *norm_out, void *stream);
+/* Bookkeeping of a greedy evaluation without auto-reset (single_rl_runner.py:218-229), per env b < B, from step
+ * t's reward, done and solved (the step's outputs): while finished[b] == 0, ret[b] += reward[b] (fp32, in step
+ * order) and, when done[b], len[b] = t + 1, ep_solved[b] = solved[b] != 0, finished[b] = 1.  A finished env is
+ * left unchanged by later steps.  The caller zeroes ret / len / ep_solved / finished before step 0.
+ * B < 0, t < 0, or a NULL pointer with B > 0: MSAT_EBADARG.  B == 0: MSAT_OK without a launch. */
+int msat_episode_track(int32_t B, int32_t t, const float *reward, const uint8_t *done, const uint8_t *solved,
+                       float *ret, int32_t *len, uint8_t *ep_solved, uint8_t *finished, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,11 @@ def _load():
     sig["msat_comm_init"] = (I, [P, I, I, P])
     sig["msat_allreduce_sum"] = (I, [P, P, Z, I, P])
     sig["msat_comm_destroy"] = (I, [P])
+    sig["msat_ppo_single_loss"] = (I, [P, I, I, P, P, P, P, P, F, F, F, I, P, P, P, P, P])
+    sig["msat_standardize_pop"] = (I, [P, Z, P, P])
+    sig["msat_clip_global_norm_workspace_doubles"] = (Z, [Z])
+    sig["msat_clip_global_norm"] = (I, [P, Z, F, P, P, P])
+    sig["msat_episode_track"] = (I, [I, I, P, P, P, P, P, P, P, P])
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -281,6 +286,11 @@ EXPORTED = (
     "msat_gather_rows",
     "msat_cycle_metrics",
     "msat_graph_bases",
+    "msat_ppo_single_loss",
+    "msat_standardize_pop",
+    "msat_clip_global_norm_workspace_doubles",
+    "msat_clip_global_norm",
+    "msat_episode_track",
     "msat_graph_templates_lds_bytes",
     "msat_graph_template_counts",
     "msat_graph_template_fill",

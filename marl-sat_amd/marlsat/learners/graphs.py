@@ -281,6 +281,18 @@ def assemble(tpl: DeviceTemplates, pool_packed: torch.Tensor, svf: torch.Tensor,
         raise ValueError("assemble: actor_only and critic_only are mutually exclusive")
     if totals is not None and critic_only:  # batch_totals plans the full or the actor-only graphs
         raise ValueError("assemble: planned totals are for the full graphs; critic_only batches size themselves")
+    return _assemble(tpl, pool_packed, svf, inst, x, critic_only, totals, actor_only)
+
+
+def assemble_critic(tpl: DeviceTemplates, pool_packed: torch.Tensor, svf: torch.Tensor, inst: torch.Tensor,
+                    x: torch.Tensor, totals: Tuple[int, int, int]) -> GraphBatch:
+    """``assemble(..., critic_only=True)`` with the batch's (var rows, clause rows, incidences) planned by
+    ``batch_totals(..., critic_only=True)``: graph 0 of every sample and no device -> host read (the single-agent
+    learner's micro-batches, which are critic-only batches throughout)."""
+    return _assemble(tpl, pool_packed, svf, inst, x, True, totals, False)
+
+
+def _assemble(tpl: DeviceTemplates, pool_packed, svf, inst, x, critic_only: bool, totals, actor_only: bool) -> GraphBatch:
     S = int(inst.shape[0])
     g0, G = (1, tpl.A) if actor_only else (0, 1 if critic_only else tpl.G)
     dev = inst.device
@@ -322,15 +334,15 @@ def assemble(tpl: DeviceTemplates, pool_packed: torch.Tensor, svf: torch.Tensor,
 
 
 def batch_totals(tpl: DeviceTemplates, inst: torch.Tensor, bounds: List[int],
-                 actor_only: bool = False) -> List[Tuple[int, int, int]]:
-    """(var rows, clause rows, incidences) of the full-sample (or, ``actor_only``, the agents'-graphs-only)
-    batches inst[bounds[i]:bounds[i+1]], the totals msat_graph_bases computes for each, from ONE
-    device -> host read for all of them (int64 sums, so an int32 overflow shows up as a total above
-    INT32_MAX, which assemble refuses)."""
+                 actor_only: bool = False, critic_only: bool = False) -> List[Tuple[int, int, int]]:
+    """(var rows, clause rows, incidences) of the full-sample (or, ``actor_only``, the agents'-graphs-only; or,
+    ``critic_only``, graph 0 alone: assemble_critic's) batches inst[bounds[i]:bounds[i+1]], the totals
+    msat_graph_bases computes for each, from ONE device -> host read for all of them (int64 sums, so an int32
+    overflow shows up as a total above INT32_MAX, which assemble refuses)."""
     if len(bounds) < 2:
         return []
     idx = inst.long()
-    tv, tc, te = tpl.counts(actor_only)
+    tv, tc, te = tpl.counts(actor_only, critic_only)
     cnt = torch.stack((tv.index_select(0, idx), tc.index_select(0, idx), te.index_select(0, idx)), 1).to(torch.int64)
     cs = torch.cat((torch.zeros((1, 3), dtype=torch.int64, device=cnt.device), torch.cumsum(cnt, 0)))
     at = cs.index_select(0, torch.tensor(bounds, dtype=torch.int64, device=cnt.device))

@@ -71,15 +71,19 @@ _SIMPLE = {  # ours -> flax (kernel, bias)
 _CELLS = {"gru_c": "update_c", "gru_vp": "update_v_pos", "gru_vn": "update_v_neg"}
 
 
-def to_flax(flat: np.ndarray, H: int, L: int, A: int, M: int, action_mode: int = 0, E: int = 16) -> Dict[str, np.ndarray]:
-    lay = layout(H, L, A, M, action_mode, E)
-    tab, _ = offsets(lay)
-    get = lambda n: flat[tab[n][0]: tab[n][0] + int(np.prod(tab[n][1]))].reshape(tab[n][1])
-    out = {}
-    for ours, fl in _SIMPLE.items():
+def _getter(flat: np.ndarray, tab):
+    return lambda n: flat[tab[n][0]: tab[n][0] + int(np.prod(tab[n][1]))].reshape(tab[n][1])
+
+
+def _simple_to_flax(get, tab, names, out) -> None:
+    for ours, fl in names.items():
         if f"{ours}_w" in tab:
             out[f"{fl}/kernel"] = get(f"{ours}_w").copy()
             out[f"{fl}/bias"] = get(f"{ours}_b").copy()
+
+
+def _encoder_to_flax(get, H: int, L: int, out) -> None:
+    """phi_v halves, the GRU cells' gate blocks and the LayerNorm rows (shared by every layout)."""
     wv, bv = get("enc.phi_v_w"), get("enc.phi_v_b")
     out["encoder/phi_v_pos/kernel"], out["encoder/phi_v_pos/bias"] = wv[:, :H].copy(), bv[:H].copy()
     out["encoder/phi_v_neg/kernel"], out["encoder/phi_v_neg/bias"] = wv[:, H:].copy(), bv[H:].copy()
@@ -95,24 +99,35 @@ def to_flax(flat: np.ndarray, H: int, L: int, A: int, M: int, action_mode: int =
     for k in range(3 * L):
         out[f"encoder/LayerNorm_{k}/scale"] = ln[k, :H].copy()
         out[f"encoder/LayerNorm_{k}/bias"] = ln[k, H:].copy()
+
+
+def to_flax(flat: np.ndarray, H: int, L: int, A: int, M: int, action_mode: int = 0, E: int = 16) -> Dict[str, np.ndarray]:
+    lay = layout(H, L, A, M, action_mode, E)
+    tab, _ = offsets(lay)
+    get = _getter(flat, tab)
+    out = {}
+    _simple_to_flax(get, tab, _SIMPLE, out)
+    _encoder_to_flax(get, H, L, out)
     out["agent_id_embedding/embedding"] = get("actor.id_emb").copy()
     return out
 
 
-def from_flax(tree: Dict[str, np.ndarray], H: int, L: int, A: int, M: int, action_mode: int = 0,
-              E: int = 16) -> np.ndarray:
-    lay = layout(H, L, A, M, action_mode, E)
-    tab, total = offsets(lay)
-    flat = np.zeros(total, np.float32)
-
+def _putter(flat: np.ndarray, tab):
     def put(n, v):
         o, shp = tab[n]
         flat[o: o + int(np.prod(shp))] = np.asarray(v, np.float32).reshape(-1)
 
-    for ours, fl in _SIMPLE.items():
+    return put
+
+
+def _simple_from_flax(put, tab, names, tree) -> None:
+    for ours, fl in names.items():
         if f"{ours}_w" in tab:
             put(f"{ours}_w", tree[f"{fl}/kernel"])
             put(f"{ours}_b", tree[f"{fl}/bias"])
+
+
+def _encoder_from_flax(put, tree, H: int, L: int) -> None:
     put("enc.phi_v_w", np.concatenate([tree["encoder/phi_v_pos/kernel"], tree["encoder/phi_v_neg/kernel"]], 1))
     put("enc.phi_v_b", np.concatenate([tree["encoder/phi_v_pos/bias"], tree["encoder/phi_v_neg/bias"]]))
     for ours, fl in _CELLS.items():
@@ -122,13 +137,22 @@ def from_flax(tree: Dict[str, np.ndarray], H: int, L: int, A: int, M: int, actio
         put(f"enc.{ours}_bh", np.concatenate([np.zeros(2 * H), tree[f"encoder/{fl}/hn/bias"]]))
     put("enc.ln", np.stack([np.concatenate([tree[f"encoder/LayerNorm_{k}/scale"], tree[f"encoder/LayerNorm_{k}/bias"]])
                             for k in range(3 * L)]))
+
+
+def from_flax(tree: Dict[str, np.ndarray], H: int, L: int, A: int, M: int, action_mode: int = 0,
+              E: int = 16) -> np.ndarray:
+    lay = layout(H, L, A, M, action_mode, E)
+    tab, total = offsets(lay)
+    flat = np.zeros(total, np.float32)
+    put = _putter(flat, tab)
+    _simple_from_flax(put, tab, _SIMPLE, tree)
+    _encoder_from_flax(put, tree, H, L)
     put("actor.id_emb", tree["agent_id_embedding/embedding"])
     return flat
 
 
-def init_flat(H: int, L: int, A: int, M: int, action_mode: int = 0, E: int = 16, seed: int = 0) -> np.ndarray:
-    """Flax-default init families: lecun-normal kernels (truncated at 2 sd), orthogonal GRU recurrent
-    kernels, zero biases, LayerNorm scale 1 / bias 0, Embed normal(1/sqrt(E))."""
+def _init_tree(shapes, H: int, seed: int) -> Dict[str, np.ndarray]:
+    """Flax-default init families over a {flax name: shape} table, drawn in the table's order."""
     rng = np.random.default_rng(seed)
 
     def lecun(i, o):
@@ -141,7 +165,6 @@ def init_flat(H: int, L: int, A: int, M: int, action_mode: int = 0, E: int = 16,
         return q * np.sign(np.diag(r))
 
     tree = {}
-    shapes = _flax_shapes(H, L, A, M, action_mode, E)
     for name, shp in shapes.items():
         if name.endswith("/bias"):
             tree[name] = np.zeros(shp)
@@ -153,10 +176,17 @@ def init_flat(H: int, L: int, A: int, M: int, action_mode: int = 0, E: int = 16,
             tree[name] = orth(H)
         else:
             tree[name] = lecun(*shp)
-    return from_flax(tree, H, L, A, M, action_mode, E)
+    return tree
 
 
-def _flax_shapes(H, L, A, M, action_mode, E):
+def init_flat(H: int, L: int, A: int, M: int, action_mode: int = 0, E: int = 16, seed: int = 0) -> np.ndarray:
+    """Flax-default init families: lecun-normal kernels (truncated at 2 sd), orthogonal GRU recurrent
+    kernels, zero biases, LayerNorm scale 1 / bias 0, Embed normal(1/sqrt(E))."""
+    return from_flax(_init_tree(_flax_shapes(H, L, A, M, action_mode, E), H, seed), H, L, A, M, action_mode, E)
+
+
+def _body_shapes(H, L):
+    """{flax name: shape} of the encoder and the critic head, in init order (shared by every layout)."""
     s = {}
 
     def dense(n, i, o, b=True):
@@ -180,6 +210,11 @@ def _flax_shapes(H, L, A, M, action_mode, E):
     dense("critic_dense_0", 6 * H, 128)
     dense("critic_dense_1", 128, 64)
     dense("critic_output", 64, 1)
+    return s, dense
+
+
+def _flax_shapes(H, L, A, M, action_mode, E):
+    s, dense = _body_shapes(H, L)
     s["agent_id_embedding/embedding"] = (A, E)
     ctx = 5 * H + E
     if action_mode == 0:
@@ -192,3 +227,53 @@ def _flax_shapes(H, L, A, M, action_mode, E):
         dense("actor_dense_1", 128, 64)
         dense("actor_output", 64, 2)
     return s
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Single-agent baseline (learners/single_gnn.py GNNSingleActorCritic): one encoder shared by the actor and the
+# critic, the parameter tree that src/runners/single_rl_runner.py:248-275 names (a GNN body, actor_dense_1 / _2,
+# actor_output and a critic head).  The encoder and critic entries are layout()'s, under the same flax names
+# (critic_dense_0 / _1, critic_output: a body trained here loads into either network); there is no id embedding.
+SINGLE_HEADS = ("actor.s0", "actor.s1", "actor.so", "crit.d0", "crit.d1", "crit.out")  # re-initialised on resume
+_SINGLE_SIMPLE = {k: v for k, v in _SIMPLE.items() if k.startswith(("enc.", "crit."))}
+_SINGLE_SIMPLE.update({"actor.s0": "actor_dense_1", "actor.s1": "actor_dense_2", "actor.so": "actor_output"})
+
+
+def single_layout(H: int, L: int) -> "OrderedDict[str, Tuple[int, ...]]":
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict(
+        (k, v) for k, v in layout(H, L, 1, 1).items() if k.startswith(("enc.", "crit.")))
+    s["actor.s0_w"], s["actor.s0_b"] = (2 * H, 128), (128,)
+    s["actor.s1_w"], s["actor.s1_b"] = (128, 64), (64,)
+    s["actor.so_w"], s["actor.so_b"] = (64, 1), (1,)
+    return s
+
+
+def single_to_flax(flat: np.ndarray, H: int, L: int) -> Dict[str, np.ndarray]:
+    tab, _ = offsets(single_layout(H, L))
+    get = _getter(flat, tab)
+    out = {}
+    _simple_to_flax(get, tab, _SINGLE_SIMPLE, out)
+    _encoder_to_flax(get, H, L, out)
+    return out
+
+
+def single_from_flax(tree: Dict[str, np.ndarray], H: int, L: int) -> np.ndarray:
+    tab, total = offsets(single_layout(H, L))
+    flat = np.zeros(total, np.float32)
+    put = _putter(flat, tab)
+    _simple_from_flax(put, tab, _SINGLE_SIMPLE, tree)
+    _encoder_from_flax(put, tree, H, L)
+    return flat
+
+
+def _single_flax_shapes(H, L):
+    s, dense = _body_shapes(H, L)
+    dense("actor_dense_1", 2 * H, 128)
+    dense("actor_dense_2", 128, 64)
+    dense("actor_output", 64, 1)
+    return s
+
+
+def single_init_flat(H: int, L: int, seed: int = 0) -> np.ndarray:
+    """init_flat's families for the single layout (the encoder and the critic draw what init_flat draws for them)."""
+    return single_from_flax(_init_tree(_single_flax_shapes(H, L), H, seed), H, L)

@@ -125,6 +125,51 @@ def load_train_state(net, state: Dict, reset_optimizer: bool = False) -> None:
     net.adam_count = int(np.asarray(adam["count"]))
 
 
+def single_train_state_dict(net, lr_schedule: bool = True) -> Dict:
+    """train_state_dict for the single-agent network (learners/single_gnn.py, params.single_layout): the same
+    TrainState state dict over that network's own parameter tree (its layout hooks)."""
+
+    def tree_of(buf):
+        return nest({k: v.astype(np.float32) for k, v in net._to_flax(buf.detach().cpu().numpy()).items()})
+
+    count = np.asarray(net.adam_count, dtype=np.int32)
+    return {
+        "step": np.asarray(net.adam_count, dtype=np.int32),
+        "params": tree_of(net.params),
+        "opt_state": {"0": {"count": count, "mu": tree_of(net.adam_m), "nu": tree_of(net.adam_v)},
+                      "1": {"count": count} if lr_schedule else {}},
+    }
+
+
+def load_single_train_state(net, state: Dict, reset_optimizer: bool = False) -> None:
+    """load_train_state for the single-agent network."""
+    import torch
+
+    def buf_of(tree):
+        return torch.from_numpy(net._from_flax(flatten(tree)))
+
+    net.params.copy_(buf_of(state["params"]))
+    if reset_optimizer:
+        net.adam_m.zero_()
+        net.adam_v.zero_()
+        net.adam_count = 0
+        return
+    adam = state["opt_state"]["0"]
+    net.adam_m.copy_(buf_of(adam["mu"]))
+    net.adam_v.copy_(buf_of(adam["nu"]))
+    net.adam_count = int(np.asarray(adam["count"]))
+
+
+def prune_checkpoints(ckpt_dir: str, prefix: str, keep: int) -> None:
+    """flax's ``keep``: only the ``keep`` highest steps of <ckpt_dir>/<prefix><step> stay."""
+    if not os.path.isdir(ckpt_dir):
+        return
+    steps = sorted(int(f[len(prefix):]) for f in os.listdir(ckpt_dir)
+                   if f.startswith(prefix) and f[len(prefix):].isdigit())
+    for s in steps[:-keep] if keep > 0 else steps:
+        os.remove(os.path.join(ckpt_dir, f"{prefix}{s}"))
+
+
 def save_checkpoint(ckpt_dir: str, target: Dict, step: int = 0, prefix: str = "latest_model_",
                     overwrite: bool = True) -> str:
     """flax.training.checkpoints.save_checkpoint analogue: writes <ckpt_dir>/<prefix><step> atomically."""
