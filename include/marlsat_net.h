@@ -451,6 +451,41 @@ int msat_clip_global_norm(float *grads, size_t n, float max_norm, double *worksp
 int msat_episode_track(int32_t B, int32_t t, const float *reward, const uint8_t *done, const uint8_t *solved,
                        float *ret, int32_t *len, uint8_t *ep_solved, uint8_t *finished, void *stream);
 
+/* ---- assignment predictor (src/learners/bc_learner.py, src/runners/bc_runner.py) ----
+ * Additive entry point: msat_version() stays 3, no struct changed.  Enqueue only. */
+/* The per-variable two-class cross-entropy (bc_learner.py:28-31, jnp.mean over (batch, variable)), its gradient,
+ * the arg-max assignment and whether that assignment satisfies the sample's formula.
+ * Layout: logits (S*V, 2) fp32, row s*V + v = variable v of sample s (graph 0's row order in a critic-only batch),
+ * at any float address; labels (S, V) u8; lits the packed pool (num_problems, num_clauses, MSAT_LIT_SLOTS) of
+ * marlsat.h; problem_idx (S) int32.
+ * Prediction: pred[s, v] = (l1 > l0) ? 1 : 0 for every row whatever its label; a tie gives 0 (jnp.argmax's lowest
+ * index) and so does a NaN.
+ * A row is valid when label is 0 or 1 and both logits are finite.  With d = l[label] - l[1 - label] in fp64:
+ * nll = max(-d, 0) + log1p(exp(-|d|)); p_other = 1 / (1 + exp(d)), taken through exp(-|d|) so that nothing
+ * overflows; dlogits[label] = -p_other / (minibatch * V), dlogits[1 - label] = +p_other / (minibatch * V): one fp32
+ * value with both signs, so a row sums to exactly 0.  Each output is rounded to fp32 once (below FLT_MIN to an fp32
+ * denormal).  `minibatch` is the number of samples the mean is over: micro-batch gradients add up to the
+ * minibatch's, as in msat_bc_loss / msat_ppo_single_loss.
+ * An invalid row gets a zero dlogits row, is not counted as correct, adds nothing to the nll and is counted in
+ * sums[3]; nothing outside the row is read for it.
+ * Per sample: sample_nll[s] = the fp64 sum of its valid rows' nll, rounded once; sample_correct[s] = its valid
+ * rows with pred == label; sample_unsat[s] = the clauses of instance clamp(problem_idx[s], 0, num_problems - 1)
+ * that pred[s] leaves false, by msat_walksat's clause rule (a code c < MSAT_LIT_ABSENT is true iff
+ * (pred[c >> 1] ^ c) & 1, MSAT_LIT_NULL is false, MSAT_LIT_ABSENT is inert; a clause with no true slot is false);
+ * sample_solved[s] = (sample_unsat[s] == 0).
+ * sums[0..4] += (sum nll, sum correct, valid rows, invalid rows, solved samples) in fp64; sums[0] adds the fp64
+ * row terms, not the rounded sample_nll.  The order of every sum is fixed by (S, V) alone: two identical calls
+ * leave bitwise identical words everywhere.  Every output word has one writer.  Two launches, no host read.
+ * Predict only: labels == NULL (then dlogits must be NULL too) writes pred, sample_unsat, sample_solved and
+ * sums[4]; sample_nll, sample_correct and sums may be NULL, and with sums NULL nothing is accumulated.
+ * S == 0: MSAT_OK without a launch.  MSAT_EBADARG: S < 0, V outside [1, 32000] (msat_walksat's bound),
+ * num_clauses < 1, num_problems < 1, minibatch < 1, labels set with dlogits NULL or the reverse, any other
+ * required pointer NULL with S > 0 (with labels set: sample_nll, sample_correct and sums too). */
+int msat_assign_loss(const float *logits, int32_t S, int32_t V, const uint8_t *labels, int32_t minibatch,
+                     const uint16_t *lits, int32_t num_problems, int32_t num_clauses, const int32_t *problem_idx,
+                     float *dlogits, uint8_t *pred, float *sample_nll, int32_t *sample_correct,
+                     int32_t *sample_unsat, uint8_t *sample_solved, double *sums, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

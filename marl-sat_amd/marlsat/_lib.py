@@ -226,6 +226,7 @@ def _load():
     sig["msat_clip_global_norm_workspace_doubles"] = (Z, [Z])
     sig["msat_clip_global_norm"] = (I, [P, Z, F, P, P, P])
     sig["msat_episode_track"] = (I, [I, I, P, P, P, P, P, P, P, P])
+    sig["msat_assign_loss"] = (I, [P, I, I, P, I, P, I, I, P, P, P, P, P, P, P, P, P])
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -291,6 +292,7 @@ EXPORTED = (
     "msat_clip_global_norm_workspace_doubles",
     "msat_clip_global_norm",
     "msat_episode_track",
+    "msat_assign_loss",
     "msat_graph_templates_lds_bytes",
     "msat_graph_template_counts",
     "msat_graph_template_fill",

@@ -277,3 +277,55 @@ def _single_flax_shapes(H, L):
 def single_init_flat(H: int, L: int, seed: int = 0) -> np.ndarray:
     """init_flat's families for the single layout (the encoder and the critic draw what init_flat draws for them)."""
     return single_from_flax(_init_tree(_single_flax_shapes(H, L), H, seed), H, L)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Assignment predictor (learners/assign_gnn.py GNNAssignmentPredictor; src/learners/bc_learner.py): the encoder
+# plus one head over the variable rows, 2H -> 128 -> 64 -> 2.  No critic, no id embedding, and no entry whose shape
+# depends on V, C or an agent split: one buffer serves every instance size.  The encoder entries are layout()'s
+# under the same flax names, so an encoder trained here loads into the other two networks by name.
+_ASSIGN_SIMPLE = {k: v for k, v in _SIMPLE.items() if k.startswith("enc.")}
+_ASSIGN_SIMPLE.update({"assign.s0": "assign_dense_0", "assign.s1": "assign_dense_1", "assign.so": "assign_output"})
+
+
+def assign_layout(H: int, L: int) -> "OrderedDict[str, Tuple[int, ...]]":
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict(
+        (k, v) for k, v in layout(H, L, 1, 1).items() if k.startswith("enc."))
+    s["assign.s0_w"], s["assign.s0_b"] = (2 * H, 128), (128,)
+    s["assign.s1_w"], s["assign.s1_b"] = (128, 64), (64,)
+    s["assign.so_w"], s["assign.so_b"] = (64, 2), (2,)
+    return s
+
+
+def assign_to_flax(flat: np.ndarray, H: int, L: int) -> Dict[str, np.ndarray]:
+    tab, _ = offsets(assign_layout(H, L))
+    get = _getter(flat, tab)
+    out = {}
+    _simple_to_flax(get, tab, _ASSIGN_SIMPLE, out)
+    _encoder_to_flax(get, H, L, out)
+    return out
+
+
+def assign_from_flax(tree: Dict[str, np.ndarray], H: int, L: int) -> np.ndarray:
+    tab, total = offsets(assign_layout(H, L))
+    flat = np.zeros(total, np.float32)
+    put = _putter(flat, tab)
+    _simple_from_flax(put, tab, _ASSIGN_SIMPLE, tree)
+    _encoder_from_flax(put, tree, H, L)
+    return flat
+
+
+def _assign_flax_shapes(H, L):
+    s, dense = _body_shapes(H, L)
+    for k in [k for k in s if k.startswith("critic_")]:  # the body's last entries: the encoder's draws come first
+        del s[k]
+    dense("assign_dense_0", 2 * H, 128)
+    dense("assign_dense_1", 128, 64)
+    dense("assign_output", 64, 2)
+    return s
+
+
+def assign_init_flat(H: int, L: int, seed: int = 0) -> np.ndarray:
+    """init_flat's families for the assign layout.  The encoder draws exactly what init_flat draws for it at the same
+    seed (it comes first in the stream); the head then draws where init_flat's critic head does."""
+    return assign_from_flax(_init_tree(_assign_flax_shapes(H, L), H, seed), H, L)

@@ -24,7 +24,39 @@ from .gnn import GNNActorCritic, HeadTape
 from .graphs import GraphBatch
 
 
-class GNNSingleActorCritic(GNNActorCritic):
+class VarRowsHead:
+    """The three-layer head over graph 0's variable rows, shared by the networks that read a critic-only batch
+    (this file's actor, assign_gnn.py's predictor): per row ``relu([H_v+ | H_v-] @ s0_w + s0_b) ->
+    relu(. @ s1_w + s1_b) -> . @ so_w + so_b`` with widths 2H -> 128 -> 64 -> ``nout``, the parameters under
+    ``<pre>.s0 / .s1 / .so``.  Mixed into a GNNActorCritic (its launch layer and parameter views)."""
+
+    def _var_rows_head(self, b: GraphBatch, Hp, Hn, ht: HeadTape, pre: str, out, nout: int):
+        H, R, e = self.H, b.Nv, self._e
+        h1, hn, h2 = e(R, 128), e(R, 128), e(R, 64)
+        # [H_v+ | H_v-] @ s0_w as two products over the weight's row blocks, added and rectified in one pass
+        self._linear(Hp, H, f"{pre}.s0_w", f"{pre}.s0_b", h1, 128, R, 128, H)
+        self._linear(Hn, H, f"{pre}.s0_w", None, hn, 128, R, 128, H, row0=H)
+        self._call("msat_bcast_add_relu", h1.data_ptr(), hn.data_ptr(), R, 1, 128)
+        self._linear(h1, 128, f"{pre}.s1_w", f"{pre}.s1_b", h2, 64, R, 64, 128)
+        self._call("msat_relu", h2.data_ptr(), h2.numel())
+        self._linear(h2, 64, f"{pre}.so_w", f"{pre}.so_b", out, nout, R, nout, 64)
+        ht.my, ht.h1, ht.h2 = (Hp, Hn), h1, h2
+        return out
+
+    def _var_rows_head_backward(self, b: GraphBatch, ht: HeadTape, dout, dHp, dHn, pre: str, nout: int):
+        H, R, e = self.H, b.Nv, self._e
+        Hp, Hn = ht.my
+        dh2, dh1 = e(R, 64), e(R, 128)
+        self._linear_backward(ht.h2, 64, f"{pre}.so_w", f"{pre}.so_b", dout, nout, R, nout, 64, dx=dh2, lddx=64)
+        self._call("msat_relu_bwd", dh2.data_ptr(), ht.h2.data_ptr(), dh2.numel())
+        self._linear_backward(ht.h1, 128, f"{pre}.s1_w", f"{pre}.s1_b", dh2, 64, R, 64, 128, dx=dh1, lddx=128)
+        self._call("msat_relu_bwd", dh1.data_ptr(), ht.h1.data_ptr(), dh1.numel())
+        # on top of what dHp / dHn already hold (the critic head's backward, or zeros)
+        self._linear_backward(Hp, H, f"{pre}.s0_w", f"{pre}.s0_b", dh1, 128, R, 128, H, dx=dHp, lddx=H, acc=1)
+        self._linear_backward(Hn, H, f"{pre}.s0_w", None, dh1, 128, R, 128, H, dx=dHn, lddx=H, acc=1, row0=H)
+
+
+class GNNSingleActorCritic(VarRowsHead, GNNActorCritic):
     """Shared-encoder actor-critic over all V variables (params.single_layout)."""
 
     def __init__(self, gnn_hidden_dim: int, gnn_num_message_passing_steps: int, num_vars: int, device=None,
@@ -58,29 +90,10 @@ class GNNSingleActorCritic(GNNActorCritic):
 
     # ------------------------------------------------------------ heads ----
     def actor_head(self, b: GraphBatch, Hp, Hn, Hc, ht: HeadTape):
-        H, R, e = self.H, b.Nv, self._e
-        h1, hn, h2, logits = e(R, 128), e(R, 128), e(R, 64), e(b.S, self.V)
-        # [H_v+ | H_v-] @ s0_w as two products over the weight's row blocks, added and rectified in one pass
-        self._linear(Hp, H, "actor.s0_w", "actor.s0_b", h1, 128, R, 128, H)
-        self._linear(Hn, H, "actor.s0_w", None, hn, 128, R, 128, H, row0=H)
-        self._call("msat_bcast_add_relu", h1.data_ptr(), hn.data_ptr(), R, 1, 128)
-        self._linear(h1, 128, "actor.s1_w", "actor.s1_b", h2, 64, R, 64, 128)
-        self._call("msat_relu", h2.data_ptr(), h2.numel())
-        self._linear(h2, 64, "actor.so_w", "actor.so_b", logits, 1, R, 1, 64)
-        ht.my, ht.h1, ht.h2 = (Hp, Hn), h1, h2
-        return logits
+        return self._var_rows_head(b, Hp, Hn, ht, "actor", self._e(b.S, self.V), 1)
 
     def actor_head_backward(self, b, ht: HeadTape, dlogits, dHp, dHn, dHc):
-        H, R, e = self.H, b.Nv, self._e
-        Hp, Hn = ht.my
-        dh2, dh1 = e(R, 64), e(R, 128)
-        self._linear_backward(ht.h2, 64, "actor.so_w", "actor.so_b", dlogits, 1, R, 1, 64, dx=dh2, lddx=64)
-        self._call("msat_relu_bwd", dh2.data_ptr(), ht.h2.data_ptr(), dh2.numel())
-        self._linear_backward(ht.h1, 128, "actor.s1_w", "actor.s1_b", dh2, 64, R, 64, 128, dx=dh1, lddx=128)
-        self._call("msat_relu_bwd", dh1.data_ptr(), ht.h1.data_ptr(), dh1.numel())
-        # on top of what the critic head's backward left in dHp / dHn
-        self._linear_backward(Hp, H, "actor.s0_w", "actor.s0_b", dh1, 128, R, 128, H, dx=dHp, lddx=H, acc=1)
-        self._linear_backward(Hn, H, "actor.s0_w", None, dh1, 128, R, 128, H, dx=dHn, lddx=H, acc=1, row0=H)
+        self._var_rows_head_backward(b, ht, dlogits, dHp, dHn, "actor", 1)
 
     def _check_heads(self, b: GraphBatch, actor: bool, critic: bool, what: str):
         """Both heads read graph 0 alone: the batch must be critic-only, its variable rows sample-major (S, V)."""

@@ -64,11 +64,17 @@ def walksat(pool, problem_idx, *, key=None, max_flips: int, noise: float = 0.5, 
 
 
 def solve_pool(pool, *, tries: int = 8, max_flips: int = 100_000, max_rounds: int = 4, noise: float = 0.5,
-               key=None) -> Dict[str, np.ndarray]:
+               key=None, init_assignments=None) -> Dict[str, np.ndarray]:
     """One solution per instance of ``pool`` by random restarts.  Round r launches ``tries`` samples for every
     instance still unsolved (samples i * tries .. i * tries + tries - 1 for the i-th of them, in instance order)
     with ``counter = key.counter + r``, so every restart is a fresh draw.  The winner of an instance is the
     lowest sample index that solved it, in its earliest solving round.  One device -> host read per round.
+
+    ``init_assignments`` ((N, V) 0/1, host or device; e.g. an assignment predictor's output): round 0 starts every
+    one of an instance's ``tries`` samples from its row instead of a random draw; the samples still differ by their
+    Philox row streams, and an instance its row already satisfies is solved with 0 flips.  Later rounds are the
+    random restarts they are without it, at the same counters.  None: every output is what it is without the
+    keyword, bit for bit.
 
     Returns host arrays over the N instances: ``solved`` bool, ``solution`` (N, V) uint8 (zeros where unsolved),
     ``flips`` int32, ``round`` int32 and ``try`` int32 (-1 where unsolved)."""
@@ -79,13 +85,20 @@ def solve_pool(pool, *, tries: int = 8, max_flips: int = 100_000, max_rounds: in
     out = {"solved": np.zeros(N, dtype=bool), "solution": np.zeros((N, V), dtype=np.uint8),
            "flips": np.full(N, -1, dtype=np.int32), "round": np.full(N, -1, dtype=np.int32),
            "try": np.full(N, -1, dtype=np.int32)}
+    init = None
+    if init_assignments is not None:
+        init = torch.as_tensor(np.asarray(init_assignments) if not torch.is_tensor(init_assignments)
+                               else init_assignments).to(device=pool.device, dtype=torch.uint8)
+        if tuple(init.shape) != (N, V):
+            raise ValueError(f"init_assignments must be (N, V) = ({N}, {V}), got {tuple(init.shape)}")
     for r in range(int(max_rounds)):
         todo = np.flatnonzero(~out["solved"])
         if todo.size == 0:
             break
         pidx = np.repeat(todo, tries)
+        start = init.repeat_interleave(tries, dim=0) if init is not None and r == 0 else None  # round 0: every instance
         x, ok, fl, _ = walksat(pool, pidx, key=Key(k.seed, (k.counter + r) & ((1 << 64) - 1)), max_flips=max_flips,
-                               noise=noise)
+                               noise=noise, assignments=start)
         okm = ok.reshape(todo.size, tries) != 0
         any_ok = okm.any(dim=1)
         # lowest solving try of each instance (a unique maximum: argmax leaves ties open)

@@ -9,6 +9,11 @@ restarts, ``msat_walksat``) searches all of its instances at once.  Every soluti
 ``SATEnv._calculate_satisfaction_explicit`` before its file is written, in the reference's format, which
 ``runners.behavioral_cloning.load_expert_data`` reads as is.  Local search is incomplete: an instance it does not
 solve (an unsatisfiable one never is) gets no file and is reported as unsolved.
+
+``--init-model <run_dir>`` (``solve_directory(init_model=...)``) starts round 0 from an assignment predictor's output
+(runners/bc_runner.py) instead of random draws: one checkpoint serves every size of the directory,
+because no parameter of that network depends on V or C.  An instance the prediction already satisfies is solved with
+0 flips; verification, the file format and the exit status are the same.
 """
 from __future__ import annotations
 
@@ -33,13 +38,40 @@ def write_sol(path: str, assignment) -> None:
         f.write(" ".join(str(int(v)) for v in np.asarray(assignment).reshape(-1)) + "\n")
 
 
+def predicted_starts(net, desc: Dict, pool, key=None):
+    """The predictor's assignment for every instance of ``pool``: (pred (N, V) u8, num_unsat (N,), solved (N,)) on
+    the device.  Its input is x = 0, or, for a model trained with INPUT: corrupted, the assignment ``env.reset``
+    draws for env n under ``key`` (what msat_walksat starts from without an initial assignment)."""
+    import torch
+
+    from ..learners.assign_learner import AssignLearner
+    from ..solvers.walksat import walksat
+
+    N, V = int(pool.num_problems), int(pool.num_vars)
+    idx = torch.arange(N, dtype=torch.int32, device=pool.device)
+    if desc.get("INPUT", "zeros") == "zeros":
+        x = torch.zeros((N, V), dtype=torch.uint8, device=pool.device)
+    else:
+        x = walksat(pool, idx, key=key, max_flips=0)[0]
+    return AssignLearner({}, net, pool).predict(idx, x)
+
+
 def solve_directory(cnf_dir: str, sol_dir: str, *, names: Optional[Sequence[str]] = None, log=None,
-                    **solve_kwargs) -> Dict[str, List[str]]:
+                    init_model: Optional[str] = None, **solve_kwargs) -> Dict[str, List[str]]:
     """Solve the ``.cnf`` files of ``cnf_dir`` (all of them, or only ``names``) and write ``<stem>.sol`` into
     ``sol_dir`` for each one solved.  ``solve_kwargs`` go to ``solve_pool`` (tries, max_flips, max_rounds, noise,
-    key).  Returns ``{"solved": [names], "unsolved": [names]}`` in directory order."""
+    key).  ``init_model``: a bc_runner run directory; its predictor, loaded once, gives round 0's starts for every
+    (V, C) group.  Returns ``{"solved": [names], "unsolved": [names]}`` in directory order (with ``init_model`` also
+    ``"starts": {name: (V,) uint8}``, the predicted assignments)."""
     from ..envs.multi_agent_sat_env import SATEnv
     from ..solvers.walksat import solve_pool
+
+    model = None
+    if init_model is not None:
+        from ..runners.bc_runner import load_predictor
+
+        model = load_predictor(init_model)
+    starts = {}
 
     problems = load_cnf_problems(cnf_dir)
     if names is not None:
@@ -50,7 +82,15 @@ def solve_directory(cnf_dir: str, sol_dir: str, *, names: Optional[Sequence[str]
     for (V, C), g in group_problems(problems).items():
         env = SATEnv(V, C, max_steps=1, vars_per_agent=V)  # one agent: only the clause check is used
         pool = env.make_pool(g["clauses"])
-        res = solve_pool(pool, **solve_kwargs)
+        note = ""
+        if model is not None:
+            pred, _, pre = predicted_starts(model[0], model[1], pool, solve_kwargs.get("key"))
+            res = solve_pool(pool, init_assignments=pred, **solve_kwargs)
+            starts.update(zip(g["names"], pred.cpu().numpy()))
+            note = (f"; the prediction alone solved {int((pre != 0).sum())}, round 0 "
+                    f"{int((res['round'] == 0).sum())}")
+        else:
+            res = solve_pool(pool, **solve_kwargs)
         _, nun = env._calculate_satisfaction_explicit(res["solution"], g["clauses"])
         valid = res["solved"] & (nun.cpu().numpy() == 0)
         if (res["solved"] & ~valid).any():
@@ -61,9 +101,12 @@ def solve_directory(cnf_dir: str, sol_dir: str, *, names: Optional[Sequence[str]
             if ok:
                 write_sol(sol_path(sol_dir, name), x)
         if log is not None:
-            log(f"V={V} C={C}: {int(valid.sum())} / {len(valid)} solved")
+            log(f"V={V} C={C}: {int(valid.sum())} / {len(valid)} solved{note}")
     order = [p["name"] for p in problems]
-    return {"solved": [n for n in order if done[n]], "unsolved": [n for n in order if not done[n]]}
+    out = {"solved": [n for n in order if done[n]], "unsolved": [n for n in order if not done[n]]}
+    if model is not None:
+        out["starts"] = starts
+    return out
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -75,6 +118,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--max-rounds", type=int, default=4, help="restart rounds")
     ap.add_argument("--noise", type=float, default=0.5, help="random-walk probability")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--init-model", default=None, help="a bc_runner run directory: its assignment predictor gives "
+                                                       "round 0's starting assignments")
     return ap
 
 
@@ -83,7 +128,7 @@ def main(argv: Optional[List[str]] = None) -> int:
 
     a = build_parser().parse_args(argv)
     res = solve_directory(a.cnf_dir, a.sol_dir, tries=a.tries, max_flips=a.max_flips, max_rounds=a.max_rounds,
-                          noise=a.noise, key=PRNGKey(a.seed), log=print)
+                          noise=a.noise, key=PRNGKey(a.seed), log=print, init_model=a.init_model)
     print(f"solved {len(res['solved'])}, unsolved {len(res['unsolved'])} of "
           f"{len(res['solved']) + len(res['unsolved'])} files in {a.cnf_dir}; solutions in {a.sol_dir}")
     for n in res["unsolved"]:
