@@ -144,8 +144,8 @@ int msat_version(void); /* 3: msat_env_state carries reset_queue / reset_serial 
                          * msat_step_out carries clock_stamps (version 1 had no such field) */
 
 /* Pack an int32 literal tensor (N,C,K) (signed, 1-based, 0 = null literal) into
- * the device pool layout uint16 (N,C,4).  Literals with |l| > V set *err_flag
- * (device int32, caller zeroes it) to 1. */
+ * the device pool layout uint16 (N,C,4).  Literals with |l| > V (INT32_MIN among
+ * them) set *err_flag (device int32, caller zeroes it) to 1. */
 int msat_pool_pack(const int32_t *lits, int32_t num_problems, int32_t num_clauses,
                    int32_t clause_width, int32_t num_vars, uint16_t *pool,
                    int32_t *err_flag, void *stream);
@@ -393,7 +393,8 @@ int msat_env_masks(const msat_env_desc *desc, const msat_pool *pool,
 int msat_clause_features(const msat_env_desc *desc, const msat_env_state *state,
                          float *clause_features, void *stream);
 
-/* Static variable features (N,V,3) float32 = [deg+/C, deg-/C, 0] per pool row. */
+/* Static variable features (N,V,3) float32 = [deg+/C, deg-/C, 0] per pool row.
+ * 8 bytes of LDS per variable: num_vars > 20480 (more than 160 KiB) is MSAT_EBADARG. */
 int msat_static_var_features(const uint16_t *pool, int32_t num_problems,
                              int32_t num_vars, int32_t num_clauses,
                              float *var_features, void *stream);

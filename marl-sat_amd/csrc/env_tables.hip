@@ -19,8 +19,9 @@ __global__ void pool_pack_kernel(const int32_t *__restrict__ lits, int NC, int K
             if (lit == 0) {
                 code = MSAT_LIT_NULL;
             } else {
-                const int a = lit < 0 ? -lit : lit;
-                if (a > V) {
+                // |lit| as unsigned: INT32_MIN has no int negation, and is out of range like any other |lit| > V
+                const uint32_t a = lit < 0 ? 0u - (uint32_t)lit : (uint32_t)lit;
+                if (a > (uint32_t)V) {
                     atomicOr(err, 1);
                     code = MSAT_LIT_NULL;
                 } else {
@@ -228,8 +229,10 @@ extern "C" int msat_static_var_features(const uint16_t *pool, int32_t num_proble
                                         int32_t num_clauses, float *var_features, void *stream) {
     MSAT_REQUIRE(pool && var_features, "NULL pointer");
     MSAT_REQUIRE(num_vars >= 1 && num_vars <= 32000 && num_clauses >= 1, "bad dims");
+    const size_t lds = (size_t)num_vars * 8;
+    MSAT_REQUIRE(lds <= 160 * 1024, "static_var_features: num_vars %d needs %zu B of LDS (> 160 KiB)", num_vars, lds);
     if (num_problems == 0) return MSAT_OK;
-    hipLaunchKernelGGL(static_var_features_kernel, dim3(num_problems), dim3(kThreads),
-                       (size_t)num_vars * 8, (hipStream_t)stream, pool, num_vars, num_clauses, var_features);
+    hipLaunchKernelGGL(static_var_features_kernel, dim3(num_problems), dim3(kThreads), lds, (hipStream_t)stream, pool,
+                       num_vars, num_clauses, var_features);
     return check_launch("static_var_features_kernel");
 }

@@ -10,7 +10,9 @@ and all 1 in the second.
 What the pools hold that the generator's do not: literal 0 slots, a variable twice in a clause with the
 same sign (the adjacency counts 2) and with both signs, an all-zero clause, clauses 2 and 1 wide,
 variables in no clause, and an agent with no related clause and no neighbour (a graph of var rows only,
-between two ordinary graphs of the batch).
+between two ordinary graphs of the batch).  The wide pools (wide257, wide300, wide513k2, wide600) hold the same
+quirks on variables and clause rows past index 255, a variable in more than 64 clauses, and more variables than
+the 256 lanes of the cold kernels' one workgroup per instance.
 """
 from __future__ import annotations
 
@@ -130,7 +132,75 @@ def learner_pool() -> IrregularPool:
     return p
 
 
-BUILDERS = {"quirks23": quirks23, "k2": k2, "k1": k1, "solo": solo}
+# ---- wide pools: more variables than one 256-thread workgroup has lanes, quirks planted past index 255
+WIDE_HOT = 70  # clauses that hold the hot variable: more than 64, one wave's worth of occurrences
+WIDE_ROW0 = 256  # first clause row of the quirk rows
+
+
+def wide_quirk_rows(V: int, K: int) -> List[List[int]]:
+    """The quirk rows of a wide pool on its top variables (1-based V, V - 1, V - 2; 0-based V - 1 >= 256): a
+    literal 0 among real literals, an all-zero clause, a variable twice with both signs, twice with one sign."""
+    T, T2, T3 = V, V - 1, V - 2
+    if K == 3:
+        return [[T, 0, -3], [0, 0, 0], [T, -T, T2], [0, 0, -T], [T2, T2, -T3]]
+    assert K == 2
+    return [[0, T], [0, 0], [T, -T], [-T2, 0], [T2, T2]]
+
+
+def _wide(name: str, V: int, C: int, K: int, vpa: int, seed: int) -> IrregularPool:
+    """Two instances.  "quirk-rows": wide_quirk_rows at clause rows 256.., variable V in the first slot of the
+    first WIDE_HOT clauses (signs alternating), and, where V >= 300, 0-based variable V - 6 moved onto V - 7 so
+    that it is in no clause.  "low-vars": literals on the variables below the last agent's first only, so the last
+    agent has no related clause and every variable from there on (all those past 455 or 559 in the two largest
+    pools, 0-based 256 in the others) is in no clause."""
+    A = -(-V // vpa)
+    base, rem = divmod(V, A)
+    last_lo = (A - 1) * base + min(A - 1, rem)  # 0-based first own variable of the last agent
+    assert C >= WIDE_ROW0 + 5 and V > 256
+    q = _clauses(V, C, K, seed)
+    q[np.arange(WIDE_HOT), 0] = np.where(np.arange(WIDE_HOT) % 2 == 0, V, -V)
+    if V >= 300:
+        iso = V - 5  # 1-based; 0-based V - 6 >= 256
+        q = np.where(np.abs(q) == iso, np.sign(q) * (iso - 1), q)
+    rows = wide_quirk_rows(V, K)
+    q[WIDE_ROW0:WIDE_ROW0 + len(rows)] = rows
+    low = _clauses(last_lo, C, K, seed + 1)
+    pool = np.stack([q, low]).astype(np.int32)
+    if V >= 300:
+        assert V - 6 in isolated_vars(pool[0], V).tolist()
+    assert isolated_vars(pool[1], V).tolist()[-(V - last_lo):] == list(range(last_lo, V))
+    assert (np.abs(pool[0]) == V).any(1).sum() > 64
+    inst, x = _samples(pool, V, V)
+    return IrregularPool(name, V, C, K, vpa, pool, ["quirk-rows", "low-vars"], inst, x)
+
+
+def wide257() -> IrregularPool:
+    """V = 257, C = 300, K = 3, vars_per_agent = 8: 33 agents (26 of 8 variables, 7 of 7); one variable past the
+    workgroup, C no multiple of 32.  The last agent owns 250..256, so no agent lies wholly past 255."""
+    return _wide("wide257", 257, 300, 3, 8, 25700)
+
+
+def wide300() -> IrregularPool:
+    """V = 300, C = 400, K = 3, vars_per_agent = 60: 5 agents; 4096 < A * D = 5000 < 16384 (the env steps it with
+    256 lanes, fewer than V).  The last agent owns 240..299."""
+    return _wide("wide300", 300, 400, 3, 60, 30000)
+
+
+def wide513k2() -> IrregularPool:
+    """V = 513, C = 704, K = 2, vars_per_agent = 64: 9 agents of 57, 2-wide clauses, C a multiple of 64, three
+    trips of a 256-lane loop over V.  The last agent owns 456..512, all past 255."""
+    return _wide("wide513k2", 513, 704, 2, 64, 51300)
+
+
+def wide600() -> IrregularPool:
+    """V = 600, C = 1800, K = 3, vars_per_agent = 40: 15 agents; A * D = 45000 >= 16384 (the env steps it with 512
+    lanes, fewer than V).  The last agent owns 560..599, all past 255."""
+    return _wide("wide600", 600, 1800, 3, 40, 60000)
+
+
+WIDE = ["wide257", "wide300", "wide513k2", "wide600"]
+BUILDERS = {"quirks23": quirks23, "k2": k2, "k1": k1, "solo": solo, "wide257": wide257, "wide300": wide300,
+            "wide513k2": wide513k2, "wide600": wide600}
 _CACHE = {}
 
 

@@ -21,6 +21,10 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = ((1, 1), (63, 65), (64, 64), (65, 130), (130, 218), (257, 7))  # (V, C)
 SS = (1, 3, 130)  # one wave of a workgroup; three of its four; 33 workgroups with a half-filled last one
+# past the launch's cap of 8192 workgroups x 4 samples: the first workgroup takes a second trip of the sample loop
+# (and of the two barriers in it) with two of its four waves live
+S_PAST_CAP = 8192 * 4 + 2
+CASES = [(V, C, S) for S in SS for V, C in SHAPES] + [(3, 2, S_PAST_CAP)]
 N = 3
 MB = 5
 ULP = 2.0 ** -23
@@ -103,14 +107,11 @@ def ref_unsat(pred, codes, pidx):
     """Clauses each sample's assignment leaves false, by msat_walksat's rule on the library's own codes."""
     S = pred.shape[0]
     Np = codes.shape[0]
-    out = np.zeros(S, np.int32)
-    for s in range(S):
-        cd = codes[min(max(int(pidx[s]), 0), Np - 1)]  # (C, 4)
-        real = cd < LIT_ABSENT
-        x = pred[s][np.where(real, cd >> 1, 0)]
-        true = real & (((x ^ cd) & 1) == 1)
-        out[s] = int((~true.any(1)).sum())
-    return out
+    cd = codes[np.clip(np.asarray(pidx, np.int64), 0, Np - 1)]  # (S, C, 4)
+    real = cd < LIT_ABSENT
+    x = pred[np.arange(S)[:, None, None], np.where(real, cd >> 1, 0)]
+    true = real & (((x ^ cd) & 1) == 1)
+    return (~true.any(2)).sum(1).astype(np.int32)
 
 
 def reference(lg, lab, S, V, minibatch, codes, pidx):
@@ -205,8 +206,7 @@ def test_small_cases_cover_every_planted_row():
     assert MB * max(V for V, _ in SHAPES) < 1535  # the +80 gap's gradient stays an fp32 normal
 
 
-@pytest.mark.parametrize("S", SS)
-@pytest.mark.parametrize("V,C", SHAPES)
+@pytest.mark.parametrize("V,C,S", CASES)
 def test_assign_loss_matches_float64(V, C, S):
     lg, lab, cl, pidx, kinds = _inputs(V, C, S)
     dpool = _pool(V, C, cl)

@@ -9,7 +9,9 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("T,B,A", [(1, 1, 1), (7, 13, 2), (32, 4096, 25), (512, 128, 5), (64, 1000, 1),
-                                   (1, 257, 2)])  # T = 1: the bootstrap value alone; B = 257: a second block of one env
+                                   (1, 257, 2),  # T = 1: the bootstrap value alone; B = 257: a second block of one env
+                                   # T B = 262146: two elements past the normalisation's cap of 1024 blocks x 256
+                                   (3, 87382, 1)])
 def test_gae_matches_oracle(T, B, A):
     from marlsat.learners.ops import gae
 

@@ -32,9 +32,9 @@ def _bits(a):
     return a.view(np.int32)
 
 
-@pytest.mark.parametrize("critic_only", [False, True], ids=["full", "critic_only"])
-@pytest.mark.parametrize("name", POOLS)
-def test_assembled_batch_equals_host_reconstruction(name, critic_only, monkeypatch):
+def check_assembled_batch(name, critic_only, monkeypatch):
+    """assemble over the named pool's samples against the host reconstruction from the oracle (shared with
+    tests/test_wide_instances_gpu.py)."""
     from marlsat import SATEnv
     from marlsat.learners import graphs
     from marlsat.learners.graphs import DeviceTemplates, assemble, batch_totals, build_templates
@@ -120,3 +120,9 @@ def test_assembled_batch_equals_host_reconstruction(name, critic_only, monkeypat
     assert torch.equal(b3.vfeat, b.vfeat[v0:]) and torch.equal(b3.cfeat, b.cfeat[c0:])
     assert torch.equal(b3.ptr, b.ptr[v0:] - t2[0][2])
     assert torch.equal(b3.cbase, b.cbase[cut * G:] - c0) and torch.equal(b3.nc, b.nc[cut * G:])
+
+
+@pytest.mark.parametrize("critic_only", [False, True], ids=["full", "critic_only"])
+@pytest.mark.parametrize("name", POOLS)
+def test_assembled_batch_equals_host_reconstruction(name, critic_only, monkeypatch):
+    check_assembled_batch(name, critic_only, monkeypatch)

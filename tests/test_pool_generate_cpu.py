@@ -18,8 +18,9 @@ from conftest import ROOT
 
 import pool_generate_replay as replay
 
-# (V, C, K): 129 and 200 cross the 128-bit hidden block; (3, 5, 3) is V == K (every clause holds every variable)
-SHAPES = [(20, 20, 3), (12, 20, 2), (6, 6, 1), (129, 300, 3), (3, 5, 3), (200, 860, 3)]
+# (V, C, K): 129 and 200 cross the 128-bit hidden block; (3, 5, 3) is V == K (every clause holds every variable);
+# 257 and 600 are more variables (and 300 and 1800 more clauses) than the kernel's workgroup has lanes
+SHAPES = [(20, 20, 3), (12, 20, 2), (6, 6, 1), (129, 300, 3), (3, 5, 3), (200, 860, 3), (257, 300, 3), (600, 1800, 3)]
 SEED, COUNTER = 0x9E3779B97F4A7C15, (7 << 32) | 3  # both halves of the key and of the counter are in use
 
 

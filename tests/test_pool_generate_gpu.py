@@ -39,7 +39,8 @@ def _same(got, want):
         np.testing.assert_array_equal(g, w, err_msg=what)
 
 
-@pytest.mark.parametrize("N,V,C,K", [(64, 20, 20, 3), (64, 12, 20, 2), (4, 129, 300, 3), (4, 200, 860, 3)])
+@pytest.mark.parametrize("N,V,C,K", [(64, 20, 20, 3), (64, 12, 20, 2), (4, 129, 300, 3), (4, 200, 860, 3),
+                                     (2, 257, 300, 3), (2, 600, 1800, 3)])
 def test_generator_equals_replay_bit_for_bit(N, V, C, K):
     want = _replay(N, V, C, K)
     if (V, C) in ((20, 20), (12, 20)):

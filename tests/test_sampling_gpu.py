@@ -82,3 +82,53 @@ def test_row_without_a_finite_logit(W, greedy):
     assert 0 <= int(act[1]) < W
     assert float(lp[1]) == 0.0 and not bool(torch.signbit(lp[1]))
     assert bool(torch.isfinite(lp).all()) and int(act.min()) >= 0 and int(act.max()) < W
+
+
+def _same_bits(a, b):
+    return np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32))
+
+
+@pytest.mark.parametrize("greedy", [True, False])
+def test_rows_past_the_grid_cap_equal_the_two_pieces(greedy):
+    """R = 32773, W = 3: five rows past the launch's cap of 8192 workgroups x 4 rows, so the first two workgroups
+    take a second trip of the row loop (one of them with a single live wave).  The whole-batch call is bitwise the
+    concatenation of the rows [0, 32768) -- one trip exactly -- and [32768, R) sampled as a piece of their own:
+    msat_sample_actions_from with row_offset 32768 for the sampled draw; the greedy pick draws no noise and takes
+    no row offset (msat_sample_actions_from has no greedy form), so its pieces are plain greedy calls, and it is
+    also the first maximum of every row."""
+    from marlsat import _lib
+
+    R, W, CUT, SEED, COUNTER = 32773, 3, 8192 * 4, 0x1234_5678_9ABC_DEF1, (7 << 32) + 5
+    rng = np.random.default_rng(R)
+    lg = (rng.standard_normal((R, W)) * 2).astype(np.float32)
+    lg[rng.random((R, W)) < 0.3] = -np.inf
+    lg[np.arange(R), rng.integers(0, W, R)] = 0.25  # a live entry in every row ...
+    lg[CUT + 1] = -np.inf  # ... but one of the second trip's: log-prob 0
+    lg[CUT + 2] = 0.5  # and a three-way tie there
+
+    def call(fn, rows, *mid):
+        n = rows.shape[0]
+        act = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+        lp = torch.full((n,), float("nan"), dtype=torch.float32, device="cuda")
+        _lib.check(getattr(_lib.lib, fn)(rows.data_ptr(), n, W, *mid, SEED, COUNTER, act.data_ptr(), lp.data_ptr(),
+                                         _lib.stream_ptr()), fn)
+        torch.cuda.synchronize()
+        return act.cpu().numpy(), lp.cpu().numpy()
+
+    d = torch.from_numpy(lg).cuda()
+    head, tail = d[:CUT].contiguous(), d[CUT:].contiguous()
+    whole = call("msat_sample_actions", d, 1 if greedy else 0)
+    if greedy:
+        pieces = [call("msat_sample_actions", head, 1), call("msat_sample_actions", tail, 1)]
+        assert np.array_equal(whole[0], np.argmax(lg, 1))
+    else:
+        pieces = [call("msat_sample_actions_from", head, 0, 1.0), call("msat_sample_actions_from", tail, CUT, 1.0)]
+        assert _same_bits(call("msat_sample_actions_from", d, 0, 1.0), whole)
+    cat = tuple(np.concatenate([p[i] for p in pieces]) for i in range(2))
+    assert _same_bits(cat, whole), np.flatnonzero(cat[0] != whole[0])[:8]
+    a, lp = whole
+    assert a.min() >= 0 and a.max() < W and lp[CUT + 1] == 0.0
+    live = np.isfinite(lg).any(1)
+    assert np.isfinite(lg[live, a[live]]).all()  # never a masked action
+    ref = torch.log_softmax(torch.from_numpy(lg[live]).double(), 1).numpy()
+    assert np.abs(lp[live] - ref[np.arange(live.sum()), a[live]]).max() <= 2e-6  # this file's bar for log-probs

@@ -18,6 +18,9 @@ pytestmark = pytest.mark.gpu
 
 VS = (1, 2, 63, 64, 65, 129, 257, 1024)  # one lane; two; 64 = the lanes, one below, one above; 3 and 5 rounds; 16
 SS = (1, 3, 130)  # one wave of a workgroup; three of its four; 33 workgroups with a half-filled last one
+# past the launch's cap of 8192 workgroups x 4 rows: the first workgroup's first three waves take a second row
+S_PAST_CAP = 8192 * 4 + 3
+CASES = [(V, S) for S in SS for V in VS] + [(2, S_PAST_CAP)]
 CLIP_EPS, ENT_COEF, VF_COEF = 0.2, 0.01, 0.5
 ULP = 2.0 ** -23
 INIT = np.array([0.5, 3.0, 7.0, 11.0])
@@ -130,8 +133,7 @@ def test_small_cases_cover_every_dedicated_row():
     assert seen == set(KINDS)
 
 
-@pytest.mark.parametrize("S", SS)
-@pytest.mark.parametrize("V", VS)
+@pytest.mark.parametrize("V,S", CASES)
 def test_single_loss_matches_float64(V, S):
     lg, act, old, adv, value, tg, kinds = _inputs(V, S)
     # the 'ratio exactly 1' rows: old_logp = the kernel's own log-probability.  A first call with old_logp = 0
