@@ -33,6 +33,8 @@
  *                               src/learners/mappo_gnn_sat_learner.py:150-164
  *   msat_walksat             <- solve_one (pysat Glucose3 -> one .sol per .cnf)  src/utils/sat_solver.py:5-29;
  *                               here a batched WalkSAT/SKC local search
+ *   msat_dpll                <- the same tool's completeness (Glucose3 decides every file): a batched DPLL
+ *                               that returns a model or the verdict UNSAT
  *   msat_solve_track / _pick <- the first-solve bookkeeping of evaluate_policy  src/runners/mappo_runner.py:30-73
  *                               (+ best-so-far assignment, flip count and the choice among restarts)
  *   msat_gae                 <- _calculate_gae + global normalisation
@@ -322,6 +324,57 @@ int msat_walksat(const uint16_t *lits, int32_t num_problems, int32_t num_vars, i
                  int32_t max_flips, uint32_t noise_p32, uint64_t seed, uint64_t counter, int32_t form,
                  uint8_t *assign_out, uint8_t *solved, int32_t *flips, int32_t *num_unsat, void *stream);
 int msat_walksat_forms(void); /* number of kernel forms; form 0 = automatic, 1..n force one */
+
+/* Batched DPLL on the device: the complete search beside msat_walksat's local search.  It decides an instance
+ * (a model, or the verdict that none exists) where the reference's expert tool runs pysat's Glucose3
+ * (src/utils/sat_solver.py).  Sample s of S searches instance clamp(problem_idx[s], 0, N-1) of the packed pool
+ * lits (N,C,4) under the cube cube[s] (cube NULL: cube 0 for every sample).  No decision depends on lane order,
+ * so a host replay of the text below reproduces every output bit for bit.
+ *   Clause truth and real slots are msat_walksat's: a code c < MSAT_LIT_ABSENT is the literal of variable c >> 1
+ *   and is true iff (x[c >> 1] ^ c) & 1 (and only where that variable is assigned); MSAT_LIT_NULL is always false;
+ *   MSAT_LIT_ABSENT slots are inert.  The real slots of a clause are those with a code below MSAT_LIT_ABSENT.
+ *   Per sample: every variable starts unassigned, L = 0, nodes = conflicts = propagations = 0.  The decision
+ *   stack holds one (variable, phase, closed) entry per level 1..L; every assigned variable carries the level
+ *   at which it was assigned.  Repeat:
+ *    1. Propagate to a fixpoint in synchronous passes (at most V + 1).  A pass judges every clause against the
+ *       assignment as it stood at the start of the pass.  A clause with no true slot and no unassigned real slot
+ *       is a conflict.  A clause with no true slot, at least one unassigned real slot and the same code in all
+ *       its unassigned real slots is a unit for that code.  Any conflict: go to 2.  No unit: the fixpoint, go
+ *       to 3.  Two units of the pass on one variable with opposite signs: a conflict, go to 2 (the pass assigns
+ *       nothing that counts).  Otherwise every unit's variable is assigned at level L so that the unit's code is
+ *       true, propagations += the number of distinct variables assigned, and the next pass runs.
+ *    2. Conflict: conflicts += 1.  Pop levels while L > 0 and the top entry is closed.  L == 0: status UNSAT,
+ *       stop.  Otherwise every variable whose level is >= L becomes unassigned.  nodes == max_nodes: status
+ *       UNKNOWN, stop.  Otherwise nodes += 1, the top entry (v, phase, open) becomes (v, phase ^ 1, closed), v is
+ *       assigned phase ^ 1 at level L, go to 1.
+ *    3. Model check: no clause is without a true slot: status SAT, assign_out = the assignment with unassigned
+ *       variables written as 0, stop.
+ *    4. Decide.  nodes == max_nodes: status UNKNOWN, stop.  cnt[.] = 0; for every open clause (one with no true
+ *       slot), with k its number of unassigned real slots and w = 4 if k == 2, else 1: cnt[code] += w for each
+ *       of its unassigned real slots (per slot, duplicates included).  v = the unassigned variable that
+ *       maximises cnt[2v] + cnt[2v+1], the lowest index on ties; phase = 1 if cnt[2v] >= cnt[2v+1], else 0.
+ *       L += 1, nodes += 1.  L <= cube_bits: phase = bit L-1 of cube[s] and the entry is pushed closed;
+ *       otherwise it is pushed open.  v is assigned phase at level L, go to 1.
+ *   A cube so fixes the phases of the first cube_bits decisions along its own path and never tries their other
+ *   branch: over the 2^cube_bits cubes of an instance the searches partition the tree.  The instance is SAT iff
+ *   some cube is SAT, UNSAT iff every cube is UNSAT, undecided otherwise (no cube SAT, some cube UNKNOWN).  A
+ *   cube whose path ends above depth cube_bits ignores its unused bits (its siblings report the same result).
+ *   Outputs per sample: status (S,) u8 MSAT_DPLL_SAT / MSAT_DPLL_UNSAT / MSAT_DPLL_UNKNOWN; assign_out (S,V) u8 a
+ *   model when status is SAT, zeros otherwise; nodes, conflicts, propagations (S,) i32.
+ * One wave per sample.  LDS per sample: 8 * num_clauses (the instance row) + 8 * num_vars (the two count arrays,
+ * u32) + 4 * num_vars (the decision stack) + 2 * num_vars (16-bit levels) + num_vars rounded up to 16 (value
+ * bytes) = 8 C + 14 V + ceil16(V) <= 65536 bytes.
+ * Enqueues only.  num_samples == 0: MSAT_OK without a launch.  MSAT_EBADARG: a NULL pointer (cube excepted) with
+ * num_samples > 0, num_vars outside [1, 32000], num_clauses < 1, num_problems < 1, num_samples < 0,
+ * max_nodes < 0, cube_bits outside [0, 30], a shape past the LDS bound.
+ * (Additive entry point: msat_version() stays 3, no struct changed.) */
+#define MSAT_DPLL_UNKNOWN 0
+#define MSAT_DPLL_SAT 1
+#define MSAT_DPLL_UNSAT 2
+int msat_dpll(const uint16_t *lits, int32_t num_problems, int32_t num_vars, int32_t num_clauses,
+              const int32_t *problem_idx, const int32_t *cube, int32_t num_samples, int32_t cube_bits,
+              int32_t max_nodes, uint8_t *status, uint8_t *assign_out, int32_t *nodes, int32_t *conflicts,
+              int32_t *propagations, void *stream);
 
 /* The policy solver's search record (marlsat/solvers/policy.py): what a policy search remembers per env row
  * while it steps B envs of V variables.  It replaces the three jnp.where selects per step with which the

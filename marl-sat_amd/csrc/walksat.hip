@@ -32,6 +32,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "wave_sat.h"
 
 namespace msat {
 namespace {
@@ -57,19 +58,6 @@ struct WsArgs {
 
 __host__ __device__ constexpr int ws_assign_bytes(int V) { return (V + 15) & ~15; }
 
-// LDS written by one lane and read by another lane of the same wave: the LDS serves a wave's operations in
-// issue order, so only the compiler has to be kept from moving them.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ int lane_rank(uint64_t b) {  // set bits of b below this lane
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-}
-
-__device__ __forceinline__ int var_of(uint32_t code) { return code < MSAT_LIT_ABSENT ? (int)(code >> 1) : -1; }
-
 __device__ __forceinline__ uint32_t on_mask(int v0, int v1, int v2, int v) {
     return (v0 == v ? 1u : 0u) | (v1 == v ? 2u : 0u) | (v2 == v ? 4u : 0u);
 }
@@ -83,12 +71,7 @@ __device__ __forceinline__ int critical_var(int v0, int v1, int v2, uint32_t tm)
 
 // Row of the sample's instance into LDS, the start assignment into LDS bytes.
 __device__ __forceinline__ void ws_stage(const WsArgs &a, int s, int lane, uint2 *row, uint8_t *x) {
-    const int p = min(max(a.problem_idx[s], 0), a.N - 1);
-    const uint2 *src = reinterpret_cast<const uint2 *>(a.lits + (size_t)p * a.C * MSAT_LIT_SLOTS);
-    for (int c = lane; c < a.C; c += 64) {
-        MSAT_DCHECK(((size_t)p * a.C + c) * MSAT_LIT_SLOTS + 3, a.lits_extent);
-        row[c] = src[c];
-    }
+    wave_stage_row(a.lits, a.problem_idx, a.N, a.C, s, lane, row, a.lits_extent);
     if (a.init_assign != nullptr) {
         for (int v = lane; v < a.V; v += 64) {
             MSAT_DCHECK((size_t)s * a.V + v, a.assign_extent);

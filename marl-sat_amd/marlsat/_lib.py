@@ -129,6 +129,7 @@ def _load():
              P, P, P],
         ),
         "msat_walksat_forms": (c_int32, []),
+        "msat_dpll": (c_int32, [P, c_int32, c_int32, c_int32, P, P, c_int32, c_int32, c_int32, P, P, P, P, P, P]),
         "msat_solve_track_init": (c_int32, [c_int32, c_int32, P, P, POINTER(SolveStateC), P]),
         "msat_solve_track": (c_int32, [c_int32, c_int32, c_int32, P, P, P, POINTER(SolveStateC), P]),
         "msat_solve_pick": (c_int32, [c_int32, c_int32, c_int32, POINTER(SolveStateC), P, P, P, P, P, P, P, P]),
@@ -355,6 +356,7 @@ EXPORTED = (
     "msat_bc_corrupt",
     "msat_walksat",
     "msat_walksat_forms",
+    "msat_dpll",
     "msat_solve_track_init",
     "msat_solve_track",
     "msat_solve_pick",

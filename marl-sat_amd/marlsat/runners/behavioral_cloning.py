@@ -130,23 +130,37 @@ def bc_settings(config: Optional[dict]) -> Dict:
             "TAU_IMPROVE": float(bc.get("TAU_IMPROVE", 0.0)),
             "SOL_DATA_DIR": bc.get("SOL_DATA_DIR", "data/uf20-91-answer"),
             "SOLVE_MISSING_EXPERTS": bool(bc.get("SOLVE_MISSING_EXPERTS", False)),
+            # ours: with SOLVE_MISSING_EXPERTS, DPLL decides what WalkSAT leaves unsolved (solve_directory(complete=True))
+            "SOLVE_MISSING_COMPLETE": bool(bc.get("SOLVE_MISSING_COMPLETE", False)),
             # ours (no reference key): micro-batches without the critic's graph (BCLearner(actor_only=True))
             "ACTOR_ONLY_GRAPHS": bool(bc.get("ACTOR_ONLY_GRAPHS", False)),
             "SAVE_PATH": bc.get("SAVE_PATH", "models/bc_pretrained")}
 
 
-def solve_missing_experts(cnf_dir: str, sol_dir: str, seed: int = 0, log=print) -> Dict[str, List[str]]:
+def solve_missing_experts(cnf_dir: str, sol_dir: str, seed: int = 0, log=print,
+                          complete: bool = False) -> Dict[str, List[str]]:
     """bc_training.SOLVE_MISSING_EXPERTS: WalkSAT on the device (utils.sat_solver.solve_directory) for the
-    ``.cnf`` files of cnf_dir that have no ``.sol`` in sol_dir; the files that have one are left alone."""
+    ``.cnf`` files of cnf_dir that have no ``.sol`` in sol_dir; the files that have one are left alone.
+    ``complete`` (bc_training.SOLVE_MISSING_COMPLETE): DPLL then decides what WalkSAT left unsolved, and the files
+    it proves unsatisfiable are logged as dropped from the BC set (no policy can ever finish them)."""
     from ..utils.sat_solver import sol_path, solve_directory
 
     names = sorted(f for f in os.listdir(cnf_dir) if f.endswith(".cnf"))
     missing = [n for n in names if not os.path.exists(sol_path(sol_dir, n))]
-    res = {"solved": [], "unsolved": []}
+    if not complete:
+        res = {"solved": [], "unsolved": []}
+        if missing:
+            res = solve_directory(cnf_dir, sol_dir, names=missing, key=PRNGKey(seed))
+        log(f"[*] experts: {len(names) - len(missing)} .sol files found, {len(res['solved'])} solved by WalkSAT, "
+            f"{len(res['unsolved'])} skipped (unsolved)")
+        return res
+    res = {"solved": [], "unsolved": [], "unsat": []}
     if missing:
-        res = solve_directory(cnf_dir, sol_dir, names=missing, key=PRNGKey(seed))
-    log(f"[*] experts: {len(names) - len(missing)} .sol files found, {len(res['solved'])} solved by WalkSAT, "
-        f"{len(res['unsolved'])} skipped (unsolved)")
+        res = solve_directory(cnf_dir, sol_dir, names=missing, key=PRNGKey(seed), complete=True)
+    log(f"[*] experts: {len(names) - len(missing)} .sol files found, {len(res['solved'])} solved by WalkSAT or DPLL, "
+        f"{len(res['unsat'])} proven unsatisfiable, {len(res['unsolved'])} skipped (undecided)")
+    for n in res["unsat"]:
+        log(f"[*] experts: {n} is unsatisfiable: dropped from the BC set")
     return res
 
 
@@ -200,7 +214,10 @@ def run(config: Dict, log=print) -> Dict:
                  r_sat=rewards.get("R_SAT", 1.0), gamma=fc.get("GAMMA", 0.99))
     cnf_dir = config.get("CNF_DATA_DIR", "data")
     if bc["SOLVE_MISSING_EXPERTS"]:
-        solve_missing_experts(cnf_dir, bc["SOL_DATA_DIR"], seed, log)
+        if bc["SOLVE_MISSING_COMPLETE"]:
+            solve_missing_experts(cnf_dir, bc["SOL_DATA_DIR"], seed, log, complete=True)
+        else:
+            solve_missing_experts(cnf_dir, bc["SOL_DATA_DIR"], seed, log)
     experts = load_expert_data(cnf_dir, bc["SOL_DATA_DIR"])
     if not experts:
         log(f"no expert (.cnf, .sol) pairs found in {cnf_dir} / {bc['SOL_DATA_DIR']}")

@@ -10,6 +10,12 @@ restarts, ``msat_walksat``) searches all of its instances at once.  Every soluti
 ``runners.behavioral_cloning.load_expert_data`` reads as is.  Local search is incomplete: an instance it does not
 solve (an unsatisfiable one never is) gets no file and is reported as unsolved.
 
+``--complete`` (``solve_directory(complete=True)``) closes that gap: the instances WalkSAT leaves unsolved go to
+``solvers.dpll.decide_pool`` (batched DPLL, ``msat_dpll``), which returns a model or the verdict
+that none exists.  Its models are verified and written like WalkSAT's; the proven-unsatisfiable names are listed
+in ``<sol_dir>/unsat.txt``; only what the node budgets (``--max-nodes``, ``--cube-bits``) leave undecided is still
+reported as unsolved, and only that makes the exit status 1.
+
 ``--init-model <run_dir>`` (``solve_directory(init_model=...)``) starts round 0 from an assignment predictor's output
 (runners/bc_runner.py) instead of random draws: one checkpoint serves every size of the directory,
 because no parameter of that network depends on V or C.  An instance the prediction already satisfies is solved with
@@ -57,12 +63,18 @@ def predicted_starts(net, desc: Dict, pool, key=None):
 
 
 def solve_directory(cnf_dir: str, sol_dir: str, *, names: Optional[Sequence[str]] = None, log=None,
-                    init_model: Optional[str] = None, **solve_kwargs) -> Dict[str, List[str]]:
+                    init_model: Optional[str] = None, complete: bool = False, dpll_kwargs: Optional[Dict] = None,
+                    **solve_kwargs) -> Dict[str, List[str]]:
     """Solve the ``.cnf`` files of ``cnf_dir`` (all of them, or only ``names``) and write ``<stem>.sol`` into
     ``sol_dir`` for each one solved.  ``solve_kwargs`` go to ``solve_pool`` (tries, max_flips, max_rounds, noise,
     key).  ``init_model``: a bc_runner run directory; its predictor, loaded once, gives round 0's starts for every
     (V, C) group.  Returns ``{"solved": [names], "unsolved": [names]}`` in directory order (with ``init_model`` also
-    ``"starts": {name: (V,) uint8}``, the predicted assignments)."""
+    ``"starts": {name: (V,) uint8}``, the predicted assignments).
+
+    ``complete``: ``solvers.dpll.decide_pool(**dpll_kwargs)`` (max_nodes, cube_bits, max_rounds) then searches the
+    instances WalkSAT left unsolved.  Its models are verified and written like WalkSAT's (their names are among
+    ``"solved"``), the proven-unsatisfiable names are returned under the new key ``"unsat"`` and written to
+    ``<sol_dir>/unsat.txt``, one per line in directory order, and ``"unsolved"`` holds only the undecided ones."""
     from ..envs.multi_agent_sat_env import SATEnv
     from ..solvers.walksat import solve_pool
 
@@ -72,6 +84,7 @@ def solve_directory(cnf_dir: str, sol_dir: str, *, names: Optional[Sequence[str]
 
         model = load_predictor(init_model)
     starts = {}
+    unsat = set()
 
     problems = load_cnf_problems(cnf_dir)
     if names is not None:
@@ -100,10 +113,37 @@ def solve_directory(cnf_dir: str, sol_dir: str, *, names: Optional[Sequence[str]
             done[name] = bool(ok)
             if ok:
                 write_sol(sol_path(sol_dir, name), x)
+        left = np.flatnonzero(~valid)
+        if complete and left.size:
+            from ..solvers.dpll import SAT, UNSAT, decide_pool
+
+            sub = g["clauses"][left]
+            dec = decide_pool(env.make_pool(sub), **(dpll_kwargs or {}))
+            _, dnun = env._calculate_satisfaction_explicit(dec["solution"], sub)
+            dnun = dnun.cpu().numpy()
+            bad = [g["names"][i] for k, i in enumerate(left) if dec["status"][k] == SAT and dnun[k] != 0]
+            if bad:
+                raise RuntimeError(f"dpll reported models that do not satisfy their formulas: {bad}")
+            for k, i in enumerate(left):
+                name = g["names"][i]
+                if dec["status"][k] == SAT:
+                    done[name] = True
+                    write_sol(sol_path(sol_dir, name), dec["solution"][k])
+                elif dec["status"][k] == UNSAT:
+                    unsat.add(name)
+            note += (f"; dpll on {left.size}: {int((dec['status'] == SAT).sum())} SAT, "
+                     f"{int((dec['status'] == UNSAT).sum())} UNSAT, {int((dec['status'] == 0).sum())} undecided")
+        elif complete:
+            note += "; dpll on 0: 0 SAT, 0 UNSAT, 0 undecided"
         if log is not None:
             log(f"V={V} C={C}: {int(valid.sum())} / {len(valid)} solved{note}")
     order = [p["name"] for p in problems]
-    out = {"solved": [n for n in order if done[n]], "unsolved": [n for n in order if not done[n]]}
+    out = {"solved": [n for n in order if done[n]],
+           "unsolved": [n for n in order if not done[n] and n not in unsat]}
+    if complete:
+        out["unsat"] = [n for n in order if n in unsat]
+        with open(os.path.join(sol_dir, "unsat.txt"), "w") as f:
+            f.write("".join(n + "\n" for n in out["unsat"]))
     if model is not None:
         out["starts"] = starts
     return out
@@ -120,6 +160,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--init-model", default=None, help="a bc_runner run directory: its assignment predictor gives "
                                                        "round 0's starting assignments")
+    ap.add_argument("--complete", action="store_true", help="DPLL on what WalkSAT leaves unsolved: a model or the "
+                                                            "verdict UNSAT (listed in <sol-dir>/unsat.txt)")
+    ap.add_argument("--max-nodes", type=int, default=None, help="--complete: branch nodes of the first DPLL round")
+    ap.add_argument("--cube-bits", type=int, default=None, help="--complete: later rounds run 2^bits cubes per "
+                                                                "instance")
     return ap
 
 
@@ -127,10 +172,21 @@ def main(argv: Optional[List[str]] = None) -> int:
     from ..random import PRNGKey
 
     a = build_parser().parse_args(argv)
-    res = solve_directory(a.cnf_dir, a.sol_dir, tries=a.tries, max_flips=a.max_flips, max_rounds=a.max_rounds,
-                          noise=a.noise, key=PRNGKey(a.seed), log=print, init_model=a.init_model)
-    print(f"solved {len(res['solved'])}, unsolved {len(res['unsolved'])} of "
-          f"{len(res['solved']) + len(res['unsolved'])} files in {a.cnf_dir}; solutions in {a.sol_dir}")
+    if not a.complete:
+        res = solve_directory(a.cnf_dir, a.sol_dir, tries=a.tries, max_flips=a.max_flips, max_rounds=a.max_rounds,
+                              noise=a.noise, key=PRNGKey(a.seed), log=print, init_model=a.init_model)
+        print(f"solved {len(res['solved'])}, unsolved {len(res['unsolved'])} of "
+              f"{len(res['solved']) + len(res['unsolved'])} files in {a.cnf_dir}; solutions in {a.sol_dir}")
+    else:
+        dk = {k: v for k, v in (("max_nodes", a.max_nodes), ("cube_bits", a.cube_bits)) if v is not None}
+        res = solve_directory(a.cnf_dir, a.sol_dir, tries=a.tries, max_flips=a.max_flips, max_rounds=a.max_rounds,
+                              noise=a.noise, key=PRNGKey(a.seed), log=print, init_model=a.init_model, complete=True,
+                              dpll_kwargs=dk)
+        total = len(res["solved"]) + len(res["unsat"]) + len(res["unsolved"])
+        print(f"solved {len(res['solved'])}, unsatisfiable {len(res['unsat'])}, undecided {len(res['unsolved'])} of "
+              f"{total} files in {a.cnf_dir}; solutions and unsat.txt in {a.sol_dir}")
+        for n in res["unsat"]:
+            print(f"unsat: {n}")
     for n in res["unsolved"]:
         print(f"unsolved: {n}")
     return 1 if res["unsolved"] else 0

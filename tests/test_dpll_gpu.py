@@ -1,0 +1,345 @@
+"""GPU: msat_dpll (batched DPLL, include/marlsat.h) bitwise against the host replay (tests/dpll_replay.py), and the
+layers above it: solvers.dpll, decide_pool's cube rule, utils.sat_solver.solve_directory(complete=True), its CLI and
+the behavioural-cloning hook.
+
+Every case compares all five outputs (status, assignment, nodes, conflicts, propagations) with the replay; every
+model is also checked with SATEnv._calculate_satisfaction_explicit, which shares nothing with the replay, and where
+V <= 14 the status is held against brute force.  Outputs are allocated with guard rows that must stay untouched."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from dpll_cases import HAND_MADE, brute_force_sat, hand_made, pigeonhole, random_pool, shared_replay
+from dpll_replay import SAT, UNKNOWN, UNSAT, combine, replay
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 2
+BIG = 200000
+NAMES = ("status", "assign", "nodes", "conflicts", "propagations")
+
+
+def device_run(clauses, V, pidx, cubes=None, cube_bits=0, max_nodes=BIG, lib=None):
+    """msat_dpll through the C-ABI on guarded output buffers -> the five outputs as numpy arrays."""
+    from marlsat import _lib
+    from marlsat.envs.multi_agent_sat_env import ProblemPool
+
+    L = lib or _lib.lib
+    pool = ProblemPool(np.asarray(clauses, np.int32), V)
+    S = len(pidx)
+    pidx_d = torch.from_numpy(np.asarray(pidx, np.int32)).cuda()
+    cube_d = None if cubes is None else torch.from_numpy(np.asarray(cubes, np.int32)).cuda()
+    st = torch.full((S + GUARD,), 0xAB, dtype=torch.uint8, device="cuda")
+    x = torch.full((S + GUARD, V), 0xAB, dtype=torch.uint8, device="cuda")
+    nd, cf, pr = (torch.full((S + GUARD,), -77, dtype=torch.int32, device="cuda") for _ in range(3))
+    rc = L.msat_dpll(pool.packed.data_ptr(), pool.num_problems, V, pool.num_clauses, pidx_d.data_ptr(),
+                     None if cube_d is None else cube_d.data_ptr(), S, cube_bits, max_nodes, st.data_ptr(),
+                     x.data_ptr(), nd.data_ptr(), cf.data_ptr(), pr.data_ptr(), _lib.stream_ptr())
+    assert rc == 0, L.msat_last_error()
+    torch.cuda.synchronize()
+    st, x, nd, cf, pr = (t.cpu().numpy() for t in (st, x, nd, cf, pr))
+    assert (st[S:] == 0xAB).all() and (x[S:] == 0xAB).all()
+    assert (nd[S:] == -77).all() and (cf[S:] == -77).all() and (pr[S:] == -77).all()
+    return st[:S], x[:S], nd[:S], cf[:S], pr[:S]
+
+
+def verify_models(clauses, V, pidx, st, x):
+    """The env's own clause check on every sample reported SAT; zeros everywhere else."""
+    from marlsat import SATEnv
+
+    clauses = np.asarray(clauses, np.int32)
+    if len(pidx) == 0:
+        return
+    env = SATEnv(V, clauses.shape[1], max_steps=1, vars_per_agent=V)
+    rows = np.clip(np.asarray(pidx, np.int64), 0, clauses.shape[0] - 1)  # the instance the kernel runs
+    _, nun = env._calculate_satisfaction_explicit(x, clauses[rows])
+    assert (nun.cpu().numpy()[st == SAT] == 0).all()
+    assert not x[st != SAT].any()
+
+
+def check_case(clauses, V, pidx, cubes=None, cube_bits=0, max_nodes=BIG, ref=None, lib=None):
+    clauses = np.asarray(clauses, np.int32)
+    pidx = np.asarray(pidx)
+    if ref is None:
+        ref = replay(clauses, V, pidx, cubes, cube_bits, max_nodes)
+    got = device_run(clauses, V, pidx, cubes, cube_bits, max_nodes, lib)
+    for name, g, r in zip(NAMES, got, ref):
+        assert g.dtype == r.dtype and np.array_equal(g, r), (name, np.flatnonzero((g != r).reshape(len(r), -1).any(1)))
+    verify_models(clauses, V, pidx, got[0], got[1])
+    return ref
+
+
+# ------------------------------------------------------------- random pools ----
+@pytest.mark.parametrize("V,C,N,seed", [(12, 80, 6, 1), (14, 60, 10, 2), (7, 63, 4, 3), (7, 64, 4, 4), (7, 65, 4, 5)])
+def test_small_random_pools_against_replay_and_brute_force(V, C, N, seed):
+    """C across one 64-clause pass and its edges; a SAT and UNSAT mix at 14 / 60."""
+    pool = random_pool(V, C, N, seed)
+    ref = check_case(pool, V, np.arange(N))
+    assert (ref[0] != UNKNOWN).all()
+    if (V, C) == (14, 60):
+        assert (ref[0] == SAT).any() and (ref[0] == UNSAT).any()
+    for n in range(N):
+        assert ref[0][n] == (SAT if brute_force_sat(pool[n], V) else UNSAT)
+
+
+def test_pigeonhole():
+    pool, V = pigeonhole(4, 3)  # binary clauses padded with literal 0 (NULL slots)
+    ref = check_case(pool, V, [0, 0])
+    assert (ref[0] == UNSAT).all() and (ref[2] > 0).all()
+
+
+@pytest.mark.parametrize("name", sorted(HAND_MADE))
+def test_hand_made_cases(name):
+    pool, V, status, nodes = hand_made(name)
+    ref = check_case(pool, V, [0])
+    assert ref[0][0] == status and (nodes is None or ref[2][0] == nodes)
+
+
+MIXED = {"50": (50, 218, 8, 11), "100": (100, 430, 4, 12)}
+
+
+def mixed(name):
+    V, C, N, seed = MIXED[name]
+    return random_pool(V, C, N, seed), V, N
+
+
+@pytest.mark.parametrize("name", sorted(MIXED))
+def test_unplanted_pools_sat_and_unsat_mix(name):
+    pool, V, N = mixed(name)
+    ref = shared_replay(("mixed", name), pool, V, np.arange(N), max_nodes=BIG)
+    assert (ref[0] == SAT).any() and (ref[0] == UNSAT).any() and (ref[0] != UNKNOWN).all()  # the replay alone first
+    check_case(pool, V, np.arange(N), ref=ref)
+
+
+def test_node_budget():
+    pool, V, N = mixed("50")
+    full = shared_replay(("mixed", "50"), pool, V, np.arange(N), max_nodes=BIG)
+    ref = check_case(pool, V, np.arange(N), max_nodes=4)
+    assert (full[2] > 4).all()
+    assert (ref[0] == UNKNOWN).all() and (ref[2] == 4).all()
+    ref = check_case(pool, V, np.arange(N), max_nodes=0)
+    assert (ref[0] == UNKNOWN).all() and (ref[2] == 0).all()
+    ref = check_case(pool, V, np.arange(N), max_nodes=37)  # some fit this budget, some do not
+    assert (ref[0] == UNKNOWN).any() and (ref[0] != UNKNOWN).any()
+
+
+def test_all_eight_cubes_per_instance():
+    pool, V, N = mixed("50")
+    single = shared_replay(("mixed", "50"), pool, V, np.arange(N), max_nodes=BIG)
+    pidx, cubes = np.repeat(np.arange(N), 8), np.tile(np.arange(8), N)
+    ref = check_case(pool, V, pidx, cubes, 3)
+    for n in range(N):
+        assert combine(ref[0][n * 8:(n + 1) * 8]) == single[0][n]
+    assert len({tuple(r) for r in np.stack(ref[2:5], 1)}) > N  # the cubes are different searches
+
+
+# ------------------------------------------------------------ planted pools ----
+@pytest.mark.parametrize("V,C,sid", [(20, 91, 0), (50, 218, 1)])
+def test_planted_pools(V, C, sid):
+    from marlsat.utils.generate_cnf_dataset import generate_problem_pool
+
+    pool = generate_problem_pool(V, C, 6, size_id=sid)
+    ref = check_case(pool, V, np.arange(12) // 2)
+    assert (ref[0] == SAT).all()
+
+
+def test_past_256_variables():
+    """V = 300, C = 1290: 16-bit levels and byte indices past 255, 21 clause passes."""
+    from marlsat.utils.generate_cnf_dataset import generate_sat_clauses
+
+    pool = np.stack([generate_sat_clauses(300, 1290, 3, 700 + i) for i in range(2)])
+    ref = check_case(pool, 300, [0, 1, 1])
+    assert (ref[0] == SAT).all() and (ref[1][:, 256:] != 0).any()
+
+
+# ------------------------------------------------------------ sample edges ----
+def test_out_of_range_problem_idx_is_clamped_by_the_kernel():
+    pool = random_pool(12, 52, 3, 21)
+    pidx = np.array([-5, -1, 0, 2, 3, 1000, 2 ** 31 - 1, -2 ** 31], dtype=np.int64)
+    ref = check_case(pool, 12, pidx.astype(np.int32))
+    same = replay(pool, 12, np.clip(pidx, 0, 2), max_nodes=BIG)
+    assert all(np.array_equal(a, b) for a, b in zip(ref, same))
+
+
+def test_no_samples_launches_nothing():
+    got = device_run(random_pool(12, 52, 3, 21), 12, np.zeros(0, np.int32))
+    assert all(len(g) == 0 for g in got)
+
+
+@pytest.mark.parametrize("S", [1, 65])
+def test_sample_count_and_order(S):
+    pool = random_pool(12, 52, 4, 22)
+    check_case(pool, 12, (np.arange(S) * 7 + 3) % 4, (np.arange(S) * 5) % 4, 2)
+
+
+# --------------------------------------------------------------- python API ----
+def test_python_api():
+    from marlsat import SATEnv
+    from marlsat.solvers import dpll
+
+    pool_np, V, N = mixed("50")
+    ref = shared_replay(("mixed", "50"), pool_np, V, np.arange(N), max_nodes=BIG)
+    pool = SATEnv(V, pool_np.shape[1], max_steps=1, vars_per_agent=10).make_pool(pool_np)
+    got = dpll(pool, np.arange(N), max_nodes=BIG)
+    assert [t.dtype for t in got] == [torch.uint8, torch.uint8, torch.int32, torch.int32, torch.int32]
+    assert all(t.is_cuda for t in got)
+    for g, r in zip(got, ref):
+        assert np.array_equal(g.cpu().numpy(), r)
+    again = dpll(pool, torch.arange(N, dtype=torch.int32).cuda(), cubes=torch.zeros(N, dtype=torch.int32).cuda(),
+                 cube_bits=0, max_nodes=BIG)
+    assert all(torch.equal(p, q) for p, q in zip(got, again))
+    empty = dpll(pool, [], max_nodes=5)
+    assert empty[0].numel() == 0 and empty[1].shape == (0, V)
+    with pytest.raises(ValueError, match="problem_idx"):
+        dpll(pool, [0, N], max_nodes=1)
+    with pytest.raises(ValueError, match="cubes"):
+        dpll(pool, [0, 1], cubes=[0], cube_bits=1, max_nodes=1)
+    with pytest.raises(ValueError, match="cubes"):
+        dpll(pool, [0, 1], cubes=[0, 2], cube_bits=1, max_nodes=1)
+    with pytest.raises(ValueError, match="cube_bits"):
+        dpll(pool, [0], cube_bits=31, max_nodes=1)
+    with pytest.raises(ValueError, match="max_nodes"):
+        dpll(pool, [0], max_nodes=-1)
+
+
+def test_decide_pool_on_a_mixed_pool():
+    from marlsat import SATEnv
+    from marlsat.solvers import decide_pool
+
+    pool_np, V, N = mixed("50")
+    ref = shared_replay(("mixed", "50"), pool_np, V, np.arange(N), max_nodes=BIG)
+    env = SATEnv(V, pool_np.shape[1], max_steps=1, vars_per_agent=10)
+    got = decide_pool(env.make_pool(pool_np))
+    assert sorted(got) == ["nodes", "solution", "status"]
+    assert np.array_equal(got["status"], ref[0]) and np.array_equal(got["nodes"], ref[2])  # round 0 decides all
+    assert np.array_equal(got["solution"], ref[1])
+    verify_models(pool_np, V, np.arange(N), got["status"], got["solution"])
+    # a first round too small for most: the cube rounds decide the rest, by the cube rule
+    got = decide_pool(env.make_pool(pool_np), max_nodes=8, cube_bits=3, max_rounds=3)
+    assert np.array_equal(got["status"], ref[0])
+    verify_models(pool_np, V, np.arange(N), got["status"], got["solution"])
+    want_nodes = np.zeros(N, np.int64)
+    left = np.arange(N)
+    for r, (bits, budget) in enumerate([(0, 8), (3, 64), (3, 512)]):  # the replay, round by round
+        K = 1 << bits
+        st, x, nd, _, _ = replay(pool_np, V, np.repeat(left, K), np.tile(np.arange(K), len(left)), bits, budget)
+        verdict = np.array([combine(st[i * K:(i + 1) * K]) for i in range(len(left))])
+        want_nodes[left] += nd.reshape(len(left), K).sum(1)
+        for i, n in enumerate(left):
+            if verdict[i] == SAT:
+                first = np.flatnonzero(st[i * K:(i + 1) * K] == SAT)[0]
+                assert np.array_equal(got["solution"][n], x[i * K + first])
+        left = left[verdict == UNKNOWN]
+    assert len(left) == 0 and np.array_equal(got["nodes"], want_nodes)
+    none = decide_pool(env.make_pool(pool_np), max_nodes=2, max_rounds=1)
+    assert (none["status"] == UNKNOWN).all() and not none["solution"].any() and (none["nodes"] == 2).all()
+
+
+# ----------------------------------------------------------- solve_directory ----
+def _write_dir(tmp_path):
+    """A dozen .cnf files of two sizes, SAT and UNSAT mixed -> (dir, sat names, unsat names), by the replay."""
+    from marlsat.utils.data_parser import write_cnf
+
+    cnf = tmp_path / "cnf"
+    cnf.mkdir()
+    sat, unsat = [], []
+    for tag, V, C, N, seed in (("a20", 20, 91, 7, 31), ("b12", 12, 56, 5, 32)):
+        pool = random_pool(V, C, N, seed)
+        st = shared_replay(("dir", tag), pool, V, np.arange(N), max_nodes=BIG)[0]
+        for i in range(N):
+            name = f"{tag}-{i}.cnf"
+            write_cnf(str(cnf / name), V, pool[i])
+            (sat if st[i] == SAT else unsat).append(name)
+    assert len(sat) >= 3 and len(unsat) >= 3
+    return str(cnf), sorted(sat), sorted(unsat)
+
+
+def test_solve_directory_complete(tmp_path):
+    from marlsat.random import PRNGKey
+    from marlsat.utils.data_parser import load_cnf_problems, parse_sol
+    from marlsat.utils.sat_solver import main, solve_directory
+    from dpll_cases import satisfied
+
+    cnf, sat, unsat = _write_dir(tmp_path)
+    sol = str(tmp_path / "sol")
+    lines = []
+    res = solve_directory(cnf, sol, tries=2, max_flips=500, max_rounds=1, key=PRNGKey(3), complete=True,
+                          log=lines.append)
+    assert res == {"solved": sat, "unsolved": [], "unsat": unsat}
+    assert sorted(os.listdir(sol)) == sorted([n[:-4] + ".sol" for n in sat] + ["unsat.txt"])
+    assert open(os.path.join(sol, "unsat.txt")).read() == "".join(n + "\n" for n in unsat)
+    problems = {p["name"]: p for p in load_cnf_problems(cnf)}
+    for n in sat:
+        x = parse_sol(os.path.join(sol, n[:-4] + ".sol"))
+        assert satisfied(x, np.asarray(problems[n]["clauses"], np.int32)).all(), n
+    assert len(lines) == 2 and all("UNSAT" in l and "undecided" in l for l in lines)
+    # the CLI: every file decided, exit 0
+    sol2 = str(tmp_path / "sol2")
+    assert main(["--cnf-dir", cnf, "--sol-dir", sol2, "--tries", "2", "--max-flips", "500", "--max-rounds", "1",
+                 "--seed", "3", "--complete"]) == 0
+    assert sorted(os.listdir(sol2)) == sorted(os.listdir(sol))
+    assert open(os.path.join(sol2, "unsat.txt")).read().split() == unsat
+    # a node budget that decides nothing WalkSAT did not solve: those stay unsolved, exit 1
+    sol3 = str(tmp_path / "sol3")
+    res3 = solve_directory(cnf, sol3, tries=2, max_flips=500, max_rounds=1, key=PRNGKey(3), complete=True,
+                           dpll_kwargs={"max_nodes": 0, "max_rounds": 1})
+    assert res3["unsat"] == [] and set(unsat) <= set(res3["unsolved"]) and open(os.path.join(sol3, "unsat.txt")).read() == ""
+    assert main(["--cnf-dir", cnf, "--sol-dir", str(tmp_path / "sol4"), "--tries", "2", "--max-flips", "500",
+                 "--max-rounds", "1", "--seed", "3", "--complete", "--max-nodes", "0", "--cube-bits", "0"]) == 1
+
+
+def test_solve_directory_without_the_flag_is_as_before(tmp_path):
+    from marlsat.random import PRNGKey
+    from marlsat.utils.sat_solver import main, solve_directory
+
+    cnf, sat, unsat = _write_dir(tmp_path)
+    sol = str(tmp_path / "sol")
+    res = solve_directory(cnf, sol, tries=4, max_flips=2000, max_rounds=2, key=PRNGKey(3))
+    assert sorted(res) == ["solved", "unsolved"]
+    assert res == {"solved": sat, "unsolved": unsat}
+    assert sorted(os.listdir(sol)) == [n[:-4] + ".sol" for n in sat]
+    sol2 = str(tmp_path / "sol2")
+    assert main(["--cnf-dir", cnf, "--sol-dir", sol2, "--tries", "4", "--max-flips", "2000", "--max-rounds", "2",
+                 "--seed", "3"]) == 1
+    assert not os.path.exists(os.path.join(sol2, "unsat.txt"))
+
+
+def test_bc_hook_logs_the_unsat_files_as_dropped(tmp_path):
+    from marlsat.runners.behavioral_cloning import load_expert_data, solve_missing_experts
+
+    cnf, sat, unsat = _write_dir(tmp_path)
+    sol = tmp_path / "sol"
+    sol.mkdir()
+    lines = []
+    res = solve_missing_experts(cnf, str(sol), seed=5, log=lines.append, complete=True)
+    assert res["solved"] == sat and res["unsat"] == unsat and res["unsolved"] == []
+    assert f"{len(unsat)} proven unsatisfiable" in lines[0]
+    assert [l for l in lines[1:]] == [f"[*] experts: {n} is unsatisfiable: dropped from the BC set" for n in unsat]
+    assert [e["name"] for e in load_expert_data(cnf, str(sol))] == sat
+
+
+# ------------------------------------------------------------- debug library ----
+def test_debug_library():
+    """libmarlsat_debug.so (MSAT_DCHECK on every global and LDS index, each launch synchronised and its checks
+    read back) gives the replay's outputs."""
+    from conftest import ROOT
+    from marlsat import _lib
+
+    path = os.path.join(ROOT, "marl-sat_amd", "marlsat", "lib", "libmarlsat_debug.so")
+    if not os.path.exists(path):
+        status = os.path.join(os.path.dirname(path), "debug_build_status.json")
+        if os.path.exists(status):
+            pytest.fail("libmarlsat_debug.so missing although a build ran: " + open(status).read())
+        pytest.skip("libmarlsat_debug.so not built (make -C marl-sat_amd debug)")
+    dbg = ctypes.CDLL(path)
+    dbg.msat_dpll.restype = ctypes.c_int32
+    dbg.msat_dpll.argtypes = _lib.lib.msat_dpll.argtypes
+    dbg.msat_last_error.restype = ctypes.c_char_p
+    pool = random_pool(14, 60, 10, 2)
+    check_case(pool, 14, np.repeat(np.arange(10), 4), np.tile(np.arange(4), 10), 2, lib=dbg)
+    php, V = pigeonhole(4, 3)
+    check_case(php, V, [0], lib=dbg)
+    check_case(random_pool(7, 65, 4, 5), 7, np.arange(4), max_nodes=3, lib=dbg)
