@@ -16,8 +16,6 @@ buffer serves batches of any V (one V per batch), DESIGN.md §17.
 """
 from __future__ import annotations
 
-import numpy as np
-
 from . import params as P
 from .gnn import GNNActorCritic, HeadTape
 from .graphs import GraphBatch
@@ -32,18 +30,8 @@ class GNNAssignmentPredictor(VarRowsHead, GNNActorCritic):
         super().__init__(gnn_hidden_dim, gnn_num_message_passing_steps, 1, 1, 0, 1, device=device, seed=seed)
         self.V = None  # no size of its own
 
-    # the layout hooks of GNNActorCritic
-    def _layout(self):
-        return P.assign_layout(self.H, self.L)
-
-    def _init_flat(self, seed: int) -> np.ndarray:
-        return P.assign_init_flat(self.H, self.L, seed)
-
-    def _from_flax(self, tree) -> np.ndarray:
-        return P.assign_from_flax(tree, self.H, self.L)
-
-    def _to_flax(self, flat: np.ndarray):
-        return P.assign_to_flax(flat, self.H, self.L)
+    def _spec(self) -> P.Spec:
+        return P.assign_spec(self.H, self.L)
 
     # ------------------------------------------------------------ heads ----
     def actor_head(self, b: GraphBatch, Hp, Hn, Hc, ht: HeadTape):

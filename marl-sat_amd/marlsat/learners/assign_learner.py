@@ -15,7 +15,6 @@ Single process.  Deviations from the reference are listed in DESIGN.md §17.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -24,36 +23,31 @@ import torch
 from .. import _lib
 from ..envs.multi_agent_sat_env import ProblemPool
 from .assign_gnn import GNNAssignmentPredictor
-from .graphs import assemble_critic, batch_totals, make_templates
-from .mappo_gnn_sat_learner import NO_BAD_STEP, activation_plan
+from .base import GRAPH0, Learner, bounds, gather_rows
 
 L_ = _lib.lib
 
 
-class AssignLearner:
+class AssignLearner(Learner):
+    """``trace``: a list receives, per Adam step, the minibatch rows, the parameters it started from, the gradient and
+    the learning rate (and the step's predictions / solved flags)."""
+
+    name = "assignment predictor"
+
     def __init__(self, config: dict, network: GNNAssignmentPredictor, pool: ProblemPool,
                  micro_bytes: Optional[float] = None, templates: str = "host"):
-        self.cfg = dict(config)
-        self.net, self.pool = network, pool
-        self.device = pool.device
+        self._init_shared(config, network, pool.device, templates, micro_bytes)
         self.V, self.C = int(pool.num_vars), int(pool.num_clauses)
         self.MB = int(config.get("BATCH_SIZE", 32))
         if self.MB < 1:
             raise ValueError(f"BATCH_SIZE={self.MB} must be >= 1")
         self.lr = float(config.get("LEARNING_RATE", 1e-4))
         # graph 0 of a template with one agent is all V variables and all C clauses
-        self.tpl = make_templates(pool, self.V, 1, templates, self.device)
-        rows = self.tpl.mean_full_rows - self.tpl.mean_actor_rows  # graph 0 alone
-        self.micro, self.chunk = activation_plan(config, rows, network.H, network.L, self.MB, self.MB, micro_bytes)
-        self.svf = pool.static_var_features()
+        self._plan_pool(pool, GRAPH0, self.V, 1, self.MB, self.MB)
         self.N = 0
         self.data: Optional[Dict[str, torch.Tensor]] = None
-        # parity instrumentation, as BCLearner.trace: a list receives, per Adam step, the minibatch rows, the
-        # parameters it started from, the gradient and the learning rate (and the step's predictions / solved flags)
-        self.trace: Optional[list] = None
         self.minibatch_losses = None  # the last epoch's per-minibatch mean losses and accuracies (numpy)
         self.minibatch_accs = None
-        self.first_bad = torch.full((1,), NO_BAD_STEP, dtype=torch.int32, device=self.device)
 
     def set_data(self, problem_idx, x, labels) -> None:
         """The dataset, kept on the device: problem_idx (N,) into the pool, x (N, V) u8 the input assignment that
@@ -73,15 +67,7 @@ class AssignLearner:
 
     def gather_rows(self, idx: torch.Tensor):
         """The dataset rows ``idx`` (int32, device) in one launch (msat_gather_rows): (pidx, x, labels)."""
-        S, dev = idx.numel(), self.device
-        srcs = [self.data["pidx"], self.data["x"], self.data["labels"]]
-        outs = [torch.empty((S,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in srcs]
-        n = len(srcs)
-        src = (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs])
-        dst = (ctypes.c_void_p * n)(*[t.data_ptr() for t in outs])
-        rb = (ctypes.c_int32 * n)(*[t[0].numel() * t.element_size() for t in srcs])
-        _lib.check(L_.msat_gather_rows(idx.data_ptr(), S, n, src, dst, rb, _lib.stream_ptr(dev)), "msat_gather_rows")
-        return outs
+        return gather_rows(idx, [self.data["pidx"], self.data["x"], self.data["labels"]])
 
     def _loss(self, logits, S, labels, mb_size, pidx, dlogits, pred, unsat, solved, sums):
         """msat_assign_loss on one micro-batch or slab (labels / dlogits None: predict only)."""
@@ -99,10 +85,9 @@ class AssignLearner:
         micro-batches) and their row totals, from ONE batch_totals(critic_only=True) read for the pass.
         -> [(start, stop, [(m0, m1, totals), ...]), ...] with positions into ``order``."""
         n, step = order.numel(), self.micro if train else self.chunk
-        cuts = [list(range(i, min(i + self.MB, n), step)) + [min(i + self.MB, n)] for i in range(0, n, self.MB)]
-        bounds = sorted({b for c in cuts for b in c})
-        sizes = dict(zip(bounds[:-1], batch_totals(self.tpl, self.data["pidx"].index_select(0, order.long()), bounds,
-                                                   critic_only=True)))
+        cuts = [bounds(i, min(i + self.MB, n), step) for i in range(0, n, self.MB)]
+        every = sorted({b for c in cuts for b in c})
+        sizes = dict(zip(every[:-1], self.totals(self.data["pidx"].index_select(0, order.long()), every)))
         return [(c[0], c[-1], [(m0, m1, sizes[m0]) for m0, m1 in zip(c[:-1], c[1:])]) for c in cuts]
 
     def minibatch_pass(self, idx: torch.Tensor, sums: torch.Tensor, mb_size: int, train: bool, micro=None):
@@ -125,7 +110,7 @@ class AssignLearner:
         for m0, m1, tot in ((a - base, b - base, t) for a, b, t in micro):
             S = m1 - m0
             pidx, x, lab = self.gather_rows(idx[m0:m1].contiguous())
-            gb = assemble_critic(self.tpl, self.pool.packed, self.svf, pidx, x, tot)
+            gb = self._batch(pidx, x, totals=tot)
             logits, _, state = net.forward(gb, critic=False, save=train)
             dlog = torch.empty_like(logits)
             self._loss(logits, S, lab, mb_size, pidx, dlog, pred[m0:m1], unsat[m0:m1], solved[m0:m1], sums)
@@ -133,16 +118,6 @@ class AssignLearner:
                 net.backward(gb, state, dlog, None)
             del state
         return pred, solved
-
-    def permutation(self, generator: torch.Generator, n: Optional[int] = None) -> torch.Tensor:
-        """A pseudo-random permutation of the N samples (or of [0, n)), keyed from the host generator's stream and
-        drawn on the device (msat_permutation), as BCLearner.permutation."""
-        n = self.N if n is None else int(n)
-        seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator))
-        perm = torch.empty((n,), dtype=torch.int32, device=self.device)
-        _lib.check(L_.msat_permutation(n, seed, 0, perm.data_ptr(), _lib.stream_ptr(self.device)),
-                   "msat_permutation")
-        return perm
 
     def _metrics(self, sums: torch.Tensor, sizes: List[int], what: str) -> Dict[str, float]:
         """The epoch's one device -> host read and the reference's averages (bc_runner.py:136-142): loss and var_acc
@@ -211,21 +186,8 @@ class AssignLearner:
         pred = torch.empty((n, V), dtype=torch.uint8, device=dev)
         unsat = torch.empty((n,), dtype=torch.int32, device=dev)
         solved = torch.empty((n,), dtype=torch.uint8, device=dev)
-        step = int(slab) if slab else self.chunk
-        bounds = list(range(0, n, step)) + [n]
-        sizes = batch_totals(self.tpl, pidx, bounds, critic_only=True)
-        for m0, m1, tot in zip(bounds[:-1], bounds[1:], sizes):
-            gb = assemble_critic(self.tpl, self.pool.packed, self.svf, pidx[m0:m1], xs[m0:m1], tot)
+        for m0, m1, tot in self.micro_batches(pidx, int(slab) if slab else self.chunk):
+            gb = self._batch(pidx[m0:m1], xs[m0:m1], totals=tot)
             logits, _, _ = self.net.forward(gb, critic=False)
             self._loss(logits, m1 - m0, None, 1, pidx[m0:m1], None, pred[m0:m1], unsat[m0:m1], solved[m0:m1], None)
         return pred, unsat, solved
-
-    def check_finite(self) -> None:
-        """The Adam guard (msat_adam_checked), as BCLearner.check_finite."""
-        bad = int(self.first_bad.item())
-        if bad != NO_BAD_STEP:
-            self.first_bad.fill_(NO_BAD_STEP)
-            raise FloatingPointError(
-                f"assignment predictor: Adam step {bad} left non-finite parameters.  A known cause: a problem with a "
-                f"variable in no clause (tests/test_isolated_variable.py; "
-                f"utils.generate_cnf_dataset.has_isolated_variable)")

@@ -18,48 +18,42 @@ job; MAPPO's tests cover the gradient all-reduce).
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Optional
 
 import torch
 
 from .. import _lib
 from ..envs.multi_agent_sat_env import ProblemPool, SATEnv
+from .base import ACTOR, FULL, Learner, gather_rows
 from .gnn import GNNActorCritic
-from .graphs import assemble, batch_totals, make_templates
-from .mappo_gnn_sat_learner import NO_BAD_STEP, activation_plan
 
 L_ = _lib.lib
 
 
-class BCLearner:
+class BCLearner(Learner):
+    """``trace``: a list receives, per Adam step, the minibatch rows, the parameters it started from, the gradient
+    and the learning rate."""
+
+    name = "BC"
+
     def __init__(self, config: dict, env: SATEnv, network: GNNActorCritic, pool: ProblemPool,
                  micro_bytes: Optional[float] = None, actor_only: bool = False, templates: str = "host"):
         if env.action_mode != 0:
             raise ValueError(f"BCLearner: action_mode {env.action_mode} is not supported: the reference's BC labels "
                              f"(compute_joint_labels_parallel_greedy) are mode-0 indices (a local variable or the "
                              f"no-op)")
-        self.cfg = dict(config)
-        self.env, self.net, self.pool = env, network, pool
-        self.device = env.device
+        self._init_shared(config, network, env.device, templates, micro_bytes)
+        self.env = env
         self.MB = int(config["MINIBATCH_SIZE"])
         if self.MB < 1:
             raise ValueError(f"MINIBATCH_SIZE={self.MB} must be >= 1")
         self.lr = float(config.get("LEARNING_RATE", 3e-4))
         self.A, self.M = env.num_agents, env.max_vars_per_agent
-        # "host": graphs.build_templates + upload; "device": graphs.build_templates_device (the same arrays)
-        self.tpl = make_templates(pool, env.num_vars, env.num_agents, templates, self.device)
         self.actor_only = bool(actor_only)
-        rows = self.tpl.mean_actor_rows if self.actor_only else self.tpl.mean_full_rows
-        self.micro, _ = activation_plan(config, rows, network.H, network.L, self.MB, 1, micro_bytes)
-        self.svf = pool.static_var_features()
+        self._plan_pool(pool, ACTOR if self.actor_only else FULL, env.num_vars, env.num_agents, self.MB, 1)
         self.N = 0
         self.data: Optional[Dict[str, torch.Tensor]] = None
-        # parity instrumentation, as MAPPOLearner.trace: a list receives, per Adam step, the minibatch rows, the
-        # parameters it started from, the gradient and the learning rate
-        self.trace: Optional[list] = None
         self.minibatch_losses = None  # the last epoch's per-minibatch mean losses (numpy, set by train_epoch)
-        self.first_bad = torch.full((1,), NO_BAD_STEP, dtype=torch.int32, device=self.device)
 
     def set_data(self, problem_idx, assignments, labels) -> None:
         """The dataset, kept on the device: problem_idx (N,) into the pool, assignments (N, V) u8, labels (N, A)
@@ -79,15 +73,7 @@ class BCLearner:
 
     def gather_rows(self, idx: torch.Tensor):
         """The dataset rows ``idx`` (int32, device) in one launch (msat_gather_rows): (pidx, x, labels)."""
-        S, dev = idx.numel(), self.device
-        srcs = [self.data["pidx"], self.data["x"], self.data["labels"]]
-        outs = [torch.empty((S,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in srcs]
-        n = len(srcs)
-        src = (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs])
-        dst = (ctypes.c_void_p * n)(*[t.data_ptr() for t in outs])
-        rb = (ctypes.c_int32 * n)(*[t[0].numel() * t.element_size() for t in srcs])
-        _lib.check(L_.msat_gather_rows(idx.data_ptr(), S, n, src, dst, rb, _lib.stream_ptr(dev)), "msat_gather_rows")
-        return outs
+        return gather_rows(idx, [self.data["pidx"], self.data["x"], self.data["labels"]])
 
     def minibatch_grad(self, idx: torch.Tensor, sums: torch.Tensor, mb_size: int) -> None:
         """net.grads = d(loss)/d(params) of the joint cross-entropy over the dataset rows ``idx``; ``sums`` (4,)
@@ -96,14 +82,11 @@ class BCLearner:
         net, dev, A, M = self.net, self.device, self.A, self.M
         idx = idx.to(torch.int32).contiguous()
         net.grads.zero_()
-        bounds = list(range(0, idx.numel(), self.micro)) + [idx.numel()]
-        # every micro-batch's row totals from one device -> host read per minibatch (MAPPOLearner.minibatch_grad)
-        sizes = batch_totals(self.tpl, self.data["pidx"].index_select(0, idx.long()), bounds, self.actor_only)
-        for m0, m1, tot in zip(bounds[:-1], bounds[1:], sizes):
+        for m0, m1, tot in self.micro_batches(self.data["pidx"].index_select(0, idx.long()), self.micro):
             mi = idx[m0:m1].contiguous()
             S = mi.numel()
             pidx, x, lab = self.gather_rows(mi)
-            gb = assemble(self.tpl, self.pool.packed, self.svf, pidx, x, False, tot, self.actor_only)
+            gb = self._batch(pidx, x, totals=tot)
             logits, _, state = net.forward(gb, critic=False, save=True)
             dlog = torch.empty_like(logits)
             rows = torch.empty((2 * S * A,), device=dev)
@@ -111,15 +94,6 @@ class BCLearner:
                                        rows.data_ptr(), sums.data_ptr(), _lib.stream_ptr(dev)), "msat_bc_loss")
             net.backward(gb, state, dlog, None)
             del state
-
-    def permutation(self, generator: torch.Generator) -> torch.Tensor:
-        """A pseudo-random permutation of the N samples, keyed from the host generator's stream and drawn on the
-        device (msat_permutation), as MAPPOLearner.permutation."""
-        seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator))
-        perm = torch.empty((self.N,), dtype=torch.int32, device=self.device)
-        _lib.check(L_.msat_permutation(self.N, seed, 0, perm.data_ptr(), _lib.stream_ptr(self.device)),
-                   "msat_permutation")
-        return perm
 
     def train_epoch(self, generator: torch.Generator) -> Dict[str, float]:
         """One pass over the dataset (behavioral_cloning.py:269-280): an Adam step per minibatch; returns the mean
@@ -149,12 +123,3 @@ class BCLearner:
         self.minibatch_losses = (s[:, 0] / (sizes * A)).numpy()  # each minibatch's mean, in Adam-step order
         loss = float(self.minibatch_losses.mean())
         return {"loss": loss, "accuracy": float(s[:, 1].sum() / max(float(s[:, 2].sum()), 1.0))}
-
-    def check_finite(self) -> None:
-        """The Adam guard (msat_adam_checked), as MAPPOLearner.check_finite."""
-        bad = int(self.first_bad.item())
-        if bad != NO_BAD_STEP:
-            self.first_bad.fill_(NO_BAD_STEP)
-            raise FloatingPointError(
-                f"BC: Adam step {bad} left non-finite parameters.  A known cause: a problem with a variable in no "
-                f"clause (tests/test_isolated_variable.py; utils.generate_cnf_dataset.has_isolated_variable)")

@@ -120,33 +120,25 @@ class GNNActorCritic(Matmul):
         self.CW = 5 * self.H + self.E
         super().__init__(torch.device(device) if device is not None else
                          torch.device("cuda", torch.cuda.current_device()))
-        self.layout = self._layout()
+        self.spec = self._spec()
+        self.layout = self.spec.layout
         self.tab, self.size = P.offsets(self.layout)
-        self.params = torch.from_numpy(self._init_flat(seed)).to(self.device)
+        self.params = torch.from_numpy(self.spec.init_flat(seed)).to(self.device)
         self.grads = torch.zeros_like(self.params)
         self.adam_m = torch.zeros_like(self.params)
         self.adam_v = torch.zeros_like(self.params)
         self.adam_count = 0
 
     # ----------------------------------------------------------- plumbing ----
-    # The four functions of params.py a network with another layout replaces (single_gnn.py).
-    def _layout(self):
-        return P.layout(self.H, self.L, self.A, self.M, self.mode, self.E)
-
-    def _init_flat(self, seed: int) -> np.ndarray:
-        return P.init_flat(self.H, self.L, self.A, self.M, self.mode, self.E, seed)
-
-    def _from_flax(self, tree) -> np.ndarray:
-        return P.from_flax(tree, self.H, self.L, self.A, self.M, self.mode, self.E)
-
-    def _to_flax(self, flat: np.ndarray):
-        return P.to_flax(flat, self.H, self.L, self.A, self.M, self.mode, self.E)
+    def _spec(self) -> P.Spec:
+        """The parameter tree (params.Spec); a network with another layout replaces it (single_gnn.py)."""
+        return P.spec(self.H, self.L, self.A, self.M, self.mode, self.E)
 
     def load_flax(self, tree):
-        self.params.copy_(torch.from_numpy(self._from_flax(tree)))
+        self.params.copy_(torch.from_numpy(self.spec.from_flax(tree)))
 
     def to_flax(self, grads: bool = False):
-        return self._to_flax((self.grads if grads else self.params).detach().cpu().numpy())
+        return self.spec.to_flax((self.grads if grads else self.params).detach().cpu().numpy())
 
     def p(self, name: str) -> torch.Tensor:
         o, shp = self.tab[name]

@@ -20,7 +20,6 @@ advantage moments / metric sums once per cycle.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from dataclasses import dataclass, field
 from typing import Dict, Optional
@@ -31,13 +30,12 @@ import torch
 from .. import _lib
 from ..envs.multi_agent_sat_env import ObsDict, ProblemPool, SATEnv, SATState
 from ..random import Key, as_key, split
+from .base import ACTOR, FULL, GRAPH0, Learner, activation_plan, gather_rows, sample_rows, spans
 from .collectives import allreduce_grads, allreduce_sums, global_moments, world_size
 from .gnn import GNNActorCritic
-from .graphs import GraphBatch, assemble, batch_totals, make_templates
 from .ops import gae as device_gae
 
 L_ = _lib.lib
-NO_BAD_STEP = 2 ** 31 - 1  # msat_adam_checked's "no non-finite update" value
 
 
 # ------------------------------------------------------------ schedules ----
@@ -63,22 +61,6 @@ def ent_coef_at(update_idx: int, config: dict) -> float:
         return float(c0)
     frac = min(1.0, max(0.0, (update_idx - start) / (n - start)))
     return float(c0 - (c0 - c1) * frac)
-
-
-def activation_plan(config: dict, rows: float, H: int, L: int, minibatch: int, num_envs: int,
-                    micro_bytes: Optional[float] = None):
-    """(micro, chunk): the training micro-batch and the inference chunk (samples) that keep the saved
-    activations inside the budget (``micro_bytes``, else MICROBATCH_BYTES); ``rows`` = a sample's mean graph
-    rows (DeviceTemplates.mean_full_rows).  Shared by the MAPPO and the behavioural-cloning learner."""
-    # saved activations per sample (encode tape, fp32, per message step): var rows Hp, Hn, NV, two
-    # G4 tapes = 12H, clause rows Hc, GIN, G4 = 7H (bounded by 12H), plus ~24H of transients
-    per_sample_train = 4.0 * L * rows * 12 * H + 4.0 * rows * 24 * H
-    per_sample_infer = 4.0 * rows * 24 * H
-    budget = micro_bytes if micro_bytes is not None else float(config.get("MICROBATCH_BYTES", 240e9))
-    cap = max(1, min(minibatch, int(budget // per_sample_train)))
-    micro = -(-minibatch // -(-minibatch // cap))  # equal micro-batches, none above the budget
-    chunk = max(1, min(num_envs, int(budget // per_sample_infer)))
-    return micro, chunk
 
 
 # ------------------------------------------------------------- wrapper ----
@@ -149,20 +131,26 @@ class RunnerState:
     rollout_counter: int = 0
 
 
-class MAPPOLearner:
-    """Device implementation of make_train_cycle's _train_cycle (see module docstring)."""
+class MAPPOLearner(Learner):
+    """Device implementation of make_train_cycle's _train_cycle (see module docstring).  ``trace``: a list makes
+    ppo_update record, per Adam step, the minibatch rows, the parameters it started from, the (all-reduced) gradient
+    and the learning rate."""
+
+    name = "MAPPO"
+    nonfinite_hint = (" -- assigned 0, that variable is a constant LayerNorm row at zero-initialised biases and its "
+                      "gradient grows ~1000x per message-passing layer past fp32 range, in the reference as here "
+                      "(tests/test_isolated_variable.py; filter the pool with generate_problem_pool(skip_isolated=True) "
+                      "or utils.generate_cnf_dataset.has_isolated_variable)")
 
     def __init__(self, config: dict, env: SATEnv, network: GNNActorCritic, pool: ProblemPool,
                  dist=None, micro_bytes: Optional[float] = None, templates: str = "host"):
         """templates: "host" builds the graph templates with graphs.build_templates and uploads them; "device"
         builds them with graphs.build_templates_device (the same arrays; the host builder for a shape past the
         kernels' LDS bound)."""
-        self.cfg = dict(config)
-        self.env, self.net = env, network
-        self.templates, self.micro_bytes = templates, micro_bytes
+        self._init_shared(config, network, env.device, templates, micro_bytes)
+        self.env = env
         self.dist = dist
         self.world = world_size(dist)
-        self.device = env.device
         self.B = int(config["NUM_ENVS"])
         self.T = int(config["NUM_STEPS"])
         self.MB = int(config["MINIBATCH_SIZE"])
@@ -174,10 +162,8 @@ class MAPPOLearner:
         self.set_pool(pool)
         self.A, self.M = env.num_agents, env.max_vars_per_agent
         self.mode = env.action_mode
-        # parity instrumentation: a list makes ppo_update record, per Adam step, the minibatch rows,
-        # the parameters it started from, the (all-reduced) gradient and the learning rate
-        self.trace: Optional[list] = None
-        self._alloc()
+        self._alloc_rollout(self.T, self.B, env.num_vars,
+                            (self.T, self.B, self.A) if self.mode == 0 else (self.T, self.B, self.A, self.M))
 
     def set_pool(self, pool: ProblemPool) -> None:
         """Train on another pool of the same (V, C, K) from now on: replaces the pool, its graph templates and its
@@ -193,33 +179,10 @@ class MAPPOLearner:
         if pool.num_vars != self.env.num_vars or pool.num_clauses != self.env.num_clauses:
             raise ValueError(f"pool is V={pool.num_vars}, C={pool.num_clauses}; env is V={self.env.num_vars}, "
                              f"C={self.env.num_clauses}")
-        net = self.net
-        self.tpl = make_templates(pool, self.env.num_vars, self.env.num_agents, self.templates, self.device)
-        self.micro, self.chunk = activation_plan(self.cfg, self.tpl.mean_full_rows, net.H, net.L, self.MB, self.B,
-                                                 self.micro_bytes)
+        self._plan_pool(pool, FULL, self.env.num_vars, self.env.num_agents, self.MB, self.B)
         # the inference chunk of an actor-only batch (policy(actor_only=True)): the same budget over fewer rows
-        _, self.actor_chunk = activation_plan(self.cfg, self.tpl.mean_actor_rows, net.H, net.L, self.MB, self.B,
-                                              self.micro_bytes)
-        self.svf = pool.static_var_features()
-        self.pool = pool
-
-    def _alloc(self):
-        T, B, V, A, M, dev = self.T, self.B, self.env.num_vars, self.A, self.M, self.device
-        act_shape = (T, B, A) if self.mode == 0 else (T, B, A, M)
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-        self.tr = {
-            "pidx": z((T, B), torch.int32), "x": z((T, B, V), torch.uint8), "action": z(act_shape, torch.int32),
-            "log_prob": z(act_shape, torch.float32), "value": z((T, B), torch.float32),
-            "reward": z((T, B), torch.float32), "done": z((T, B), torch.uint8), "solved": z((T, B), torch.uint8),
-            "num_unsatisfied": z((T, B), torch.int32), "episode_step": z((T, B), torch.int32),
-        }
-        self.adv = z((T, B), torch.float32)
-        self.targets = z((T, B), torch.float32)
-        self.last_val = z((B,), torch.float32)
-        self.mom_ws = z((2 * 1024 + 2,), torch.float64)
-        self.moments = z((2,), torch.float64)
-        # fail-loud guard: the smallest Adam count whose update left a parameter non-finite (INT32_MAX: none)
-        self.first_bad = torch.full((1,), NO_BAD_STEP, dtype=torch.int32, device=dev)
+        _, self.actor_chunk = activation_plan(self.cfg, sample_rows(self.tpl, ACTOR), self.net.H, self.net.L, self.MB,
+                                              self.B, self.micro_bytes)
 
     # ------------------------------------------------------------ helpers ----
     def init_runner_state(self, key) -> RunnerState:
@@ -228,11 +191,6 @@ class MAPPOLearner:
         k_reset, k_run = split(k, 2)
         obs, st = self.env.reset_from_pool(self.pool, self.B, k_reset)
         return RunnerState(st, obs, k_run, 0)
-
-    def _batch(self, pidx: torch.Tensor, x: torch.Tensor, critic_only: bool = False, totals=None,
-               actor_only: bool = False) -> GraphBatch:
-        return assemble(self.tpl, self.pool.packed, self.svf, pidx.contiguous(), x.contiguous(), critic_only, totals,
-                        actor_only)
 
     def policy(self, st: SATState, key: Key, greedy: bool = False, critic: bool = True, temperature: float = 1.0,
                row_offset: Optional[int] = None, actor_only: bool = False):
@@ -261,9 +219,8 @@ class MAPPOLearner:
         W = M + 1 if self.mode == 0 else 2
         # the chunk boundaries decide the sampled actions when the chunk index is in the counter (below)
         chunk = self.actor_chunk if actor_only and (greedy or row_offset is not None) else self.chunk
-        for c, b0 in enumerate(range(0, B, chunk)):
-            b1 = min(B, b0 + chunk)
-            gb = self._batch(st.problem_idx[b0:b1], st.variable_assignments[b0:b1], actor_only=actor_only)
+        for c, (b0, b1) in enumerate(spans(B, chunk)):
+            gb = self._batch(st.problem_idx[b0:b1], st.variable_assignments[b0:b1], ACTOR if actor_only else FULL)
             logits, value, _ = self.net.forward(gb, critic=critic)
             if critic:
                 val[b0:b1] = value
@@ -290,10 +247,8 @@ class MAPPOLearner:
     def critic_values(self, pidx: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
         n = pidx.shape[0]
         out = torch.empty((n,), dtype=torch.float32, device=self.device)
-        step = self.chunk * (self.A + 1)  # critic-only samples are ~A+1 times smaller
-        for b0 in range(0, n, step):
-            b1 = min(n, b0 + step)
-            _, v, _ = self.net.forward(self._batch(pidx[b0:b1], x[b0:b1], critic_only=True), actor=False)
+        for b0, b1 in spans(n, self.chunk * (self.A + 1)):  # critic-only samples are ~A+1 times smaller
+            _, v, _ = self.net.forward(self._batch(pidx[b0:b1], x[b0:b1], GRAPH0), actor=False)
             out[b0:b1] = v
         return out
 
@@ -337,11 +292,7 @@ class MAPPOLearner:
         A, M = self.A, self.M
         idx = idx.to(torch.int32)
         net.grads.zero_()
-        # every micro-batch's row totals from one device -> host read per minibatch (assemble would
-        # otherwise read each batch's totals back, and the GPU idled while the host caught up)
-        bounds = list(range(0, idx.numel(), self.micro)) + [idx.numel()]
-        sizes = batch_totals(self.tpl, self.tr["pidx"].reshape(-1).index_select(0, idx.long()), bounds)
-        for m0, m1, tot in zip(bounds[:-1], bounds[1:], sizes):
+        for m0, m1, tot in self.micro_batches(self.tr["pidx"].reshape(-1).index_select(0, idx.long()), self.micro):
             mi = idx[m0:m1]
             S = mi.numel()
             pidx, x, act, olp, g_, vold, tg = self.gather_rows(mi)
@@ -361,25 +312,8 @@ class MAPPOLearner:
     def gather_rows(self, idx: torch.Tensor):
         """The transition rows ``idx`` (int32, device) of the flat (T*B) buffers, in one launch
         (msat_gather_rows): (pidx, x, action, log_prob, advantage, value, target)."""
-        S, dev = idx.numel(), self.device
-        srcs = [self.tr["pidx"], self.tr["x"], self.tr["action"], self.tr["log_prob"], self.adv, self.tr["value"],
-                self.targets]
-        outs = [torch.empty((S,) + tuple(t.shape[2:]), dtype=t.dtype, device=dev) for t in srcs]
-        n = len(srcs)
-        src = (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs])
-        dst = (ctypes.c_void_p * n)(*[t.data_ptr() for t in outs])
-        rb = (ctypes.c_int32 * n)(*[t[0, 0].numel() * t.element_size() for t in srcs])
-        _lib.check(L_.msat_gather_rows(idx.data_ptr(), S, n, src, dst, rb, _lib.stream_ptr(dev)), "msat_gather_rows")
-        return outs
-
-    def permutation(self, generator: torch.Generator) -> torch.Tensor:
-        """A pseudo-random permutation of the T*B transition rows (learner:576), keyed from the host
-        generator's stream and drawn on the device (msat_permutation)."""
-        N = self.T * self.B
-        seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator))
-        perm = torch.empty((N,), dtype=torch.int32, device=self.device)
-        _lib.check(L_.msat_permutation(N, seed, 0, perm.data_ptr(), _lib.stream_ptr(self.device)), "msat_permutation")
-        return perm
+        return gather_rows(idx, [self.tr["pidx"], self.tr["x"], self.tr["action"], self.tr["log_prob"], self.adv,
+                                 self.tr["value"], self.targets], lead=2)
 
     def ppo_update(self, update_idx: int, generator: torch.Generator):
         c, net, dev = self.cfg, self.net, self.device
@@ -409,20 +343,6 @@ class MAPPOLearner:
         losses[..., 1] /= MB * A * w
         losses[..., 2] /= n_ent * w
         return losses, ent
-
-    def check_finite(self) -> None:
-        """One read per cycle of the Adam guard (msat_adam_checked): raise instead of carrying non-finite
-        parameters into the next cycle (the loop of mappo_runner.py:313-317 would train on NaN silently, as
-        the reference does)."""
-        bad = int(self.first_bad.item())
-        if bad != NO_BAD_STEP:
-            self.first_bad.fill_(NO_BAD_STEP)
-            raise FloatingPointError(
-                f"MAPPO: Adam step {bad} left non-finite parameters.  A known cause: a pool instance with a variable "
-                f"in no clause -- assigned 0, that variable is a constant LayerNorm row at zero-initialised biases and "
-                f"its gradient grows ~1000x per message-passing layer past fp32 range, in the reference as here "
-                f"(tests/test_isolated_variable.py; filter the pool with generate_problem_pool(skip_isolated=True) or "
-                f"utils.generate_cnf_dataset.has_isolated_variable)")
 
     # ------------------------------------------------------------ metrics ----
     def metrics(self, losses, ent):

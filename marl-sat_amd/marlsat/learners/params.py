@@ -12,7 +12,7 @@ kernels consume together:
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Dict, Tuple
+from typing import Dict, NamedTuple, Tuple
 
 import numpy as np
 
@@ -101,15 +101,49 @@ def _encoder_to_flax(get, H: int, L: int, out) -> None:
         out[f"encoder/LayerNorm_{k}/bias"] = ln[k, H:].copy()
 
 
+class Spec(NamedTuple):
+    """One network's parameter tree, described once: the flat layout, the {ours -> flax} table of its dense layers,
+    the {flax name: shape} table in init order, and whether it has the agent id embedding."""
+    H: int
+    L: int
+    layout: "OrderedDict[str, Tuple[int, ...]]"
+    names: Dict[str, str]
+    shapes: Dict[str, Tuple[int, ...]]
+    id_emb: bool = False
+
+    def to_flax(self, flat: np.ndarray) -> Dict[str, np.ndarray]:
+        tab, _ = offsets(self.layout)
+        get = _getter(flat, tab)
+        out = {}
+        _simple_to_flax(get, tab, self.names, out)
+        _encoder_to_flax(get, self.H, self.L, out)
+        if self.id_emb:
+            out["agent_id_embedding/embedding"] = get("actor.id_emb").copy()
+        return out
+
+    def from_flax(self, tree: Dict[str, np.ndarray]) -> np.ndarray:
+        tab, total = offsets(self.layout)
+        flat = np.zeros(total, np.float32)
+        put = _putter(flat, tab)
+        _simple_from_flax(put, tab, self.names, tree)
+        _encoder_from_flax(put, tree, self.H, self.L)
+        if self.id_emb:
+            put("actor.id_emb", tree["agent_id_embedding/embedding"])
+        return flat
+
+    def init_flat(self, seed: int = 0) -> np.ndarray:
+        """Flax-default init families: lecun-normal kernels (truncated at 2 sd), orthogonal GRU recurrent
+        kernels, zero biases, LayerNorm scale 1 / bias 0, Embed normal(1/sqrt(E)); drawn in ``shapes``' order."""
+        return self.from_flax(_init_tree(self.shapes, self.H, seed))
+
+
+def spec(H: int, L: int, A: int, M: int, action_mode: int = 0, E: int = 16) -> Spec:
+    """GNNActorCritic's tree (learners/gnn.py)."""
+    return Spec(H, L, layout(H, L, A, M, action_mode, E), _SIMPLE, _flax_shapes(H, L, A, M, action_mode, E), True)
+
+
 def to_flax(flat: np.ndarray, H: int, L: int, A: int, M: int, action_mode: int = 0, E: int = 16) -> Dict[str, np.ndarray]:
-    lay = layout(H, L, A, M, action_mode, E)
-    tab, _ = offsets(lay)
-    get = _getter(flat, tab)
-    out = {}
-    _simple_to_flax(get, tab, _SIMPLE, out)
-    _encoder_to_flax(get, H, L, out)
-    out["agent_id_embedding/embedding"] = get("actor.id_emb").copy()
-    return out
+    return spec(H, L, A, M, action_mode, E).to_flax(flat)
 
 
 def _putter(flat: np.ndarray, tab):
@@ -141,14 +175,7 @@ def _encoder_from_flax(put, tree, H: int, L: int) -> None:
 
 def from_flax(tree: Dict[str, np.ndarray], H: int, L: int, A: int, M: int, action_mode: int = 0,
               E: int = 16) -> np.ndarray:
-    lay = layout(H, L, A, M, action_mode, E)
-    tab, total = offsets(lay)
-    flat = np.zeros(total, np.float32)
-    put = _putter(flat, tab)
-    _simple_from_flax(put, tab, _SIMPLE, tree)
-    _encoder_from_flax(put, tree, H, L)
-    put("actor.id_emb", tree["agent_id_embedding/embedding"])
-    return flat
+    return spec(H, L, A, M, action_mode, E).from_flax(tree)
 
 
 def _init_tree(shapes, H: int, seed: int) -> Dict[str, np.ndarray]:
@@ -180,9 +207,7 @@ def _init_tree(shapes, H: int, seed: int) -> Dict[str, np.ndarray]:
 
 
 def init_flat(H: int, L: int, A: int, M: int, action_mode: int = 0, E: int = 16, seed: int = 0) -> np.ndarray:
-    """Flax-default init families: lecun-normal kernels (truncated at 2 sd), orthogonal GRU recurrent
-    kernels, zero biases, LayerNorm scale 1 / bias 0, Embed normal(1/sqrt(E))."""
-    return from_flax(_init_tree(_flax_shapes(H, L, A, M, action_mode, E), H, seed), H, L, A, M, action_mode, E)
+    return spec(H, L, A, M, action_mode, E).init_flat(seed)
 
 
 def _body_shapes(H, L):
@@ -248,24 +273,6 @@ def single_layout(H: int, L: int) -> "OrderedDict[str, Tuple[int, ...]]":
     return s
 
 
-def single_to_flax(flat: np.ndarray, H: int, L: int) -> Dict[str, np.ndarray]:
-    tab, _ = offsets(single_layout(H, L))
-    get = _getter(flat, tab)
-    out = {}
-    _simple_to_flax(get, tab, _SINGLE_SIMPLE, out)
-    _encoder_to_flax(get, H, L, out)
-    return out
-
-
-def single_from_flax(tree: Dict[str, np.ndarray], H: int, L: int) -> np.ndarray:
-    tab, total = offsets(single_layout(H, L))
-    flat = np.zeros(total, np.float32)
-    put = _putter(flat, tab)
-    _simple_from_flax(put, tab, _SINGLE_SIMPLE, tree)
-    _encoder_from_flax(put, tree, H, L)
-    return flat
-
-
 def _single_flax_shapes(H, L):
     s, dense = _body_shapes(H, L)
     dense("actor_dense_1", 2 * H, 128)
@@ -274,9 +281,21 @@ def _single_flax_shapes(H, L):
     return s
 
 
+def single_spec(H: int, L: int) -> Spec:
+    """GNNSingleActorCritic's tree.  The encoder and the critic draw what init_flat draws for them."""
+    return Spec(H, L, single_layout(H, L), _SINGLE_SIMPLE, _single_flax_shapes(H, L))
+
+
+def single_to_flax(flat: np.ndarray, H: int, L: int) -> Dict[str, np.ndarray]:
+    return single_spec(H, L).to_flax(flat)
+
+
+def single_from_flax(tree: Dict[str, np.ndarray], H: int, L: int) -> np.ndarray:
+    return single_spec(H, L).from_flax(tree)
+
+
 def single_init_flat(H: int, L: int, seed: int = 0) -> np.ndarray:
-    """init_flat's families for the single layout (the encoder and the critic draw what init_flat draws for them)."""
-    return single_from_flax(_init_tree(_single_flax_shapes(H, L), H, seed), H, L)
+    return single_spec(H, L).init_flat(seed)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -297,24 +316,6 @@ def assign_layout(H: int, L: int) -> "OrderedDict[str, Tuple[int, ...]]":
     return s
 
 
-def assign_to_flax(flat: np.ndarray, H: int, L: int) -> Dict[str, np.ndarray]:
-    tab, _ = offsets(assign_layout(H, L))
-    get = _getter(flat, tab)
-    out = {}
-    _simple_to_flax(get, tab, _ASSIGN_SIMPLE, out)
-    _encoder_to_flax(get, H, L, out)
-    return out
-
-
-def assign_from_flax(tree: Dict[str, np.ndarray], H: int, L: int) -> np.ndarray:
-    tab, total = offsets(assign_layout(H, L))
-    flat = np.zeros(total, np.float32)
-    put = _putter(flat, tab)
-    _simple_from_flax(put, tab, _ASSIGN_SIMPLE, tree)
-    _encoder_from_flax(put, tree, H, L)
-    return flat
-
-
 def _assign_flax_shapes(H, L):
     s, dense = _body_shapes(H, L)
     for k in [k for k in s if k.startswith("critic_")]:  # the body's last entries: the encoder's draws come first
@@ -325,7 +326,19 @@ def _assign_flax_shapes(H, L):
     return s
 
 
+def assign_spec(H: int, L: int) -> Spec:
+    """GNNAssignmentPredictor's tree.  The encoder draws exactly what init_flat draws for it at the same seed (it comes
+    first in the stream); the head then draws where init_flat's critic head does."""
+    return Spec(H, L, assign_layout(H, L), _ASSIGN_SIMPLE, _assign_flax_shapes(H, L))
+
+
+def assign_to_flax(flat: np.ndarray, H: int, L: int) -> Dict[str, np.ndarray]:
+    return assign_spec(H, L).to_flax(flat)
+
+
+def assign_from_flax(tree: Dict[str, np.ndarray], H: int, L: int) -> np.ndarray:
+    return assign_spec(H, L).from_flax(tree)
+
+
 def assign_init_flat(H: int, L: int, seed: int = 0) -> np.ndarray:
-    """init_flat's families for the assign layout.  The encoder draws exactly what init_flat draws for it at the same
-    seed (it comes first in the stream); the head then draws where init_flat's critic head does."""
-    return assign_from_flax(_init_tree(_assign_flax_shapes(H, L), H, seed), H, L)
+    return assign_spec(H, L).init_flat(seed)

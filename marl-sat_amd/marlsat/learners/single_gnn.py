@@ -65,23 +65,13 @@ class GNNSingleActorCritic(VarRowsHead, GNNActorCritic):
         super().__init__(gnn_hidden_dim, gnn_num_message_passing_steps, 1, num_vars, 0, num_vars, device=device,
                          seed=seed)
 
-    # the layout hooks of GNNActorCritic
-    def _layout(self):
-        return P.single_layout(self.H, self.L)
-
-    def _init_flat(self, seed: int) -> np.ndarray:
-        return P.single_init_flat(self.H, self.L, seed)
-
-    def _from_flax(self, tree) -> np.ndarray:
-        return P.single_from_flax(tree, self.H, self.L)
-
-    def _to_flax(self, flat: np.ndarray):
-        return P.single_to_flax(flat, self.H, self.L)
+    def _spec(self) -> P.Spec:
+        return P.single_spec(self.H, self.L)
 
     def reset_heads(self, seed: int) -> None:
         """Both heads back to ``seed``'s initial draw (the resume rule, single_rl_runner.py:248-275); the optimiser
         state is the caller's to clear."""
-        fresh = torch.from_numpy(self._init_flat(seed)).to(self.device)
+        fresh = torch.from_numpy(self.spec.init_flat(seed)).to(self.device)
         for head in P.SINGLE_HEADS:
             for sfx in ("_w", "_b"):
                 o, shp = self.tab[head + sfx]

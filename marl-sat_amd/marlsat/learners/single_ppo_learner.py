@@ -17,7 +17,6 @@ Single process only.  Deviations from the reference are listed in DESIGN.md §16
 """
 from __future__ import annotations
 
-import ctypes
 from dataclasses import dataclass
 from typing import Dict, Optional
 
@@ -26,8 +25,7 @@ import torch
 from .. import _lib
 from ..envs.multi_agent_sat_env import ProblemPool, SATEnv, SATState
 from ..random import Key, as_key, split
-from .graphs import assemble, assemble_critic, batch_totals, make_templates
-from .mappo_gnn_sat_learner import NO_BAD_STEP, activation_plan
+from .base import GRAPH0, Learner, gather_rows, spans
 from .ops import gae as device_gae
 from .single_gnn import GNNSingleActorCritic
 
@@ -67,7 +65,13 @@ class SingleRunnerState:
     rng: Key
 
 
-class SinglePPOLearner:
+class SinglePPOLearner(Learner):
+    """``trace``: a list receives, per Adam step, the minibatch rows, the parameters it started from, the normalised
+    advantages, the gradient before and after the clip, the norm before the clip (a device scalar) and the learning
+    rate; and per reset and env step its key."""
+
+    name = "single PPO"
+
     def __init__(self, config: dict, env: SATEnv, network: GNNSingleActorCritic, pool: ProblemPool,
                  micro_bytes: Optional[float] = None, templates: str = "host"):
         if env.num_agents != 1 or env.action_mode != 0 or env.reward_mode != _lib.REWARD_SINGLE_DELTA:
@@ -76,9 +80,8 @@ class SinglePPOLearner:
         if pool.num_vars != env.num_vars or pool.num_clauses != env.num_clauses:
             raise ValueError(f"pool is V={pool.num_vars}, C={pool.num_clauses}; env is V={env.num_vars}, "
                              f"C={env.num_clauses}")
-        self.cfg = dict(config)
-        self.env, self.net, self.pool = env, network, pool
-        self.device = env.device
+        self._init_shared(config, network, env.device, templates, micro_bytes)
+        self.env = env
         self.B, self.T = int(config["NUM_ENVS"]), int(config["NUM_STEPS"])
         self.V = env.num_vars
         self.n_minibatches, self.epochs = int(config["NUM_MINIBATCHES"]), int(config["UPDATE_EPOCHS"])
@@ -90,34 +93,12 @@ class SinglePPOLearner:
         self.max_norm = max_grad_norm(config)
         if not (0.0 < self.max_norm < float("inf")):
             raise ValueError(f"MAX_GRAD_NORM must be positive and finite, got {self.max_norm}")
-        self.tpl = make_templates(pool, env.num_vars, 1, templates, self.device)
-        rows = self.tpl.mean_full_rows - self.tpl.mean_actor_rows  # graph 0 alone
-        self.micro, self.chunk = activation_plan(config, rows, network.H, network.L, self.MB, self.B, micro_bytes)
-        self.svf = pool.static_var_features()
-        # parity instrumentation, as BCLearner.trace: a list receives, per Adam step, the minibatch rows, the
-        # parameters it started from, the normalised advantages, the gradient before and after the clip, the norm
-        # before the clip (a device scalar) and the learning rate
-        self.trace: Optional[list] = None
+        self._plan_pool(pool, GRAPH0, env.num_vars, 1, self.MB, self.B)
         self.minibatch_terms = None  # the last update's per-minibatch (actor, vl, ent) means, Adam-step order
         self.grad_norms = None  # the last update's pre-clip norms, Adam-step order (numpy)
-        self._alloc()
-
-    def _alloc(self):
-        T, B, V, dev = self.T, self.B, self.V, self.device
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-        self.tr = {
-            "pidx": z((T, B), torch.int32), "x": z((T, B, V), torch.uint8), "action": z((T, B), torch.int32),
-            "log_prob": z((T, B), torch.float32), "value": z((T, B), torch.float32),
-            "reward": z((T, B), torch.float32), "done": z((T, B), torch.uint8), "solved": z((T, B), torch.uint8),
-            "num_unsatisfied": z((T, B), torch.int32), "episode_step": z((T, B), torch.int32),
-        }
-        self.adv = z((T, B), torch.float32)
-        self.targets = z((T, B), torch.float32)
-        self.last_val = z((B,), torch.float32)
-        self.mom_ws = z((2 * 1024 + 2,), torch.float64)
-        self.moments = z((2,), torch.float64)
-        self.clip_ws = z((int(L_.msat_clip_global_norm_workspace_doubles(self.net.size)),), torch.float64)
-        self.first_bad = torch.full((1,), NO_BAD_STEP, dtype=torch.int32, device=dev)
+        self._alloc_rollout(self.T, self.B, self.V, (self.T, self.B))
+        self.clip_ws = torch.zeros((int(L_.msat_clip_global_norm_workspace_doubles(self.net.size)),),
+                                   dtype=torch.float64, device=self.device)
 
     # -------------------------------------------------------------- policy ----
     def init_runner_state(self, key) -> SingleRunnerState:
@@ -140,11 +121,8 @@ class SinglePPOLearner:
         act = torch.empty((B, 1), dtype=torch.int32, device=dev)
         logp = torch.empty((B,), dtype=torch.float32, device=dev)
         val = torch.empty((B,), dtype=torch.float32, device=dev)
-        for c, b0 in enumerate(range(0, B, self.chunk)):
-            b1 = min(B, b0 + self.chunk)
-            gb = assemble(self.tpl, self.pool.packed, self.svf, st.problem_idx[b0:b1].contiguous(),
-                          st.variable_assignments[b0:b1].contiguous(), critic_only=True)
-            logits, value, _ = self.net.forward(gb)
+        for c, (b0, b1) in enumerate(spans(B, self.chunk)):
+            logits, value, _ = self.net.forward(self._batch(st.problem_idx[b0:b1], st.variable_assignments[b0:b1]))
             val[b0:b1] = value
             _lib.check(L_.msat_sample_actions(logits.data_ptr(), b1 - b0, V, 1 if greedy else 0, key.seed,
                                               (key.counter << 16) + c, act[b0:b1].data_ptr(), logp[b0:b1].data_ptr(),
@@ -153,11 +131,9 @@ class SinglePPOLearner:
 
     def values(self, st: SATState) -> torch.Tensor:
         out = torch.empty((st.num_envs,), dtype=torch.float32, device=self.device)
-        for b0 in range(0, st.num_envs, self.chunk):
-            b1 = min(st.num_envs, b0 + self.chunk)
-            gb = assemble(self.tpl, self.pool.packed, self.svf, st.problem_idx[b0:b1].contiguous(),
-                          st.variable_assignments[b0:b1].contiguous(), critic_only=True)
-            _, v, _ = self.net.forward(gb, actor=False)
+        for b0, b1 in spans(st.num_envs, self.chunk):
+            _, v, _ = self.net.forward(self._batch(st.problem_idx[b0:b1], st.variable_assignments[b0:b1]),
+                                       actor=False)
             out[b0:b1] = v
         return out
 
@@ -195,15 +171,8 @@ class SinglePPOLearner:
     def gather_rows(self, idx: torch.Tensor):
         """The transition rows ``idx`` (int32, device) of the flat (T*B) buffers in one launch (msat_gather_rows):
         (pidx, x, action, log_prob, advantage, target)."""
-        S, dev = idx.numel(), self.device
-        srcs = [self.tr["pidx"], self.tr["x"], self.tr["action"], self.tr["log_prob"], self.adv, self.targets]
-        outs = [torch.empty((S,) + tuple(t.shape[2:]), dtype=t.dtype, device=dev) for t in srcs]
-        n = len(srcs)
-        src = (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs])
-        dst = (ctypes.c_void_p * n)(*[t.data_ptr() for t in outs])
-        rb = (ctypes.c_int32 * n)(*[t[0, 0].numel() * t.element_size() for t in srcs])
-        _lib.check(L_.msat_gather_rows(idx.data_ptr(), S, n, src, dst, rb, _lib.stream_ptr(dev)), "msat_gather_rows")
-        return outs
+        return gather_rows(idx, [self.tr["pidx"], self.tr["x"], self.tr["action"], self.tr["log_prob"], self.adv,
+                                 self.targets], lead=2)
 
     def minibatch_grad(self, idx: torch.Tensor, sums: torch.Tensor) -> torch.Tensor:
         """net.grads = d(loss)/d(params) of the PPO loss (learner:118-158) over the flat transition rows ``idx``;
@@ -219,11 +188,9 @@ class SinglePPOLearner:
         _lib.check(L_.msat_moments(adv.data_ptr(), MB, self.moments.data_ptr(), self.mom_ws.data_ptr(), st),
                    "msat_moments")
         _lib.check(L_.msat_standardize_pop(adv.data_ptr(), MB, self.moments.data_ptr(), st), "msat_standardize_pop")
-        bounds = list(range(0, MB, self.micro)) + [MB]
-        sizes = batch_totals(self.tpl, pidx, bounds, critic_only=True)  # the minibatch loop's one host read
-        for m0, m1, tot in zip(bounds[:-1], bounds[1:], sizes):
+        for m0, m1, tot in self.micro_batches(pidx, self.micro):  # the minibatch loop's one host read
             S = m1 - m0
-            gb = assemble_critic(self.tpl, self.pool.packed, self.svf, pidx[m0:m1], x[m0:m1], tot)
+            gb = self._batch(pidx[m0:m1], x[m0:m1], totals=tot)
             logits, value, state = net.forward(gb, save=True)
             dlog, dval = torch.empty_like(logits), torch.empty_like(value)
             rows = torch.empty((3 * S,), device=dev)
@@ -235,14 +202,6 @@ class SinglePPOLearner:
             net.backward(gb, state, dlog, dval)
             del state
         return adv
-
-    def permutation(self, generator: torch.Generator) -> torch.Tensor:
-        """A pseudo-random permutation of the T*B transition rows (learner:165), as MAPPOLearner.permutation."""
-        N = self.T * self.B
-        seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator))
-        perm = torch.empty((N,), dtype=torch.int32, device=self.device)
-        _lib.check(L_.msat_permutation(N, seed, 0, perm.data_ptr(), _lib.stream_ptr(self.device)), "msat_permutation")
-        return perm
 
     def ppo_update(self, generator: torch.Generator) -> Dict[str, float]:
         """learner:161-195 -> the cycle's loss quadruple (means over the minibatches): total, value, policy,
@@ -280,17 +239,6 @@ class SinglePPOLearner:
                  - float(c["ENT_COEF"]) * self.minibatch_terms[:, 2]).mean()
         return {"loss_total": float(total), "loss_value": float(vl), "loss_policy": float(actor),
                 "entropy": float(ent), "grad_norm": float(self.grad_norms.mean())}
-
-    def check_finite(self) -> None:
-        """The Adam guard (msat_adam_checked), as MAPPOLearner.check_finite: a NaN or inf gradient passes the clip
-        as NaN and is reported here."""
-        bad = int(self.first_bad.item())
-        if bad != NO_BAD_STEP:
-            self.first_bad.fill_(NO_BAD_STEP)
-            raise FloatingPointError(
-                f"single PPO: Adam step {bad} left non-finite parameters.  A known cause: a pool instance with a "
-                f"variable in no clause (tests/test_isolated_variable.py; "
-                f"utils.generate_cnf_dataset.has_isolated_variable)")
 
     # ------------------------------------------------------------- metrics ----
     def rollout_stats(self) -> Dict[str, float]:

@@ -135,7 +135,7 @@ def resume(net, path: str, seed: int, log=print) -> None:
     st = ck.restore_checkpoint(path, "cycle_", None)
     if st is None:
         raise FileNotFoundError(f"TRAIN_PARAMS.RESUME_CKPT_PATH={path!r} holds no cycle_<n> checkpoint")
-    ck.load_single_train_state(net, st, reset_optimizer=True)
+    ck.load_train_state(net, st, reset_optimizer=True)
     net.reset_heads(seed)
     log(f"resumed the GNN body from {path}; actor / critic heads and optimiser state re-initialised")
 
@@ -192,7 +192,7 @@ def run(config: Dict, log=print) -> Dict:
     g = torch.Generator().manual_seed(seed)
     best_solve, best_len = -1.0, float("inf")
     n_cycles, anneal = s["NUM_CYCLES"], s["ANNEAL_LR"]
-    state_dict = lambda: ck.single_train_state_dict(net, anneal)
+    state_dict = lambda: ck.train_state_dict(net, anneal)
     t0 = time.time()
     last_tr, last_ev = {}, {}
     with open(log_path, "w", encoding="utf-8") as f:

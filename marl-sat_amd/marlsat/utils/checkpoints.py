@@ -86,14 +86,11 @@ def flatten(tree: Dict, prefix: str = "") -> Dict[str, np.ndarray]:
 
 # ------------------------------------------------------- train state ----
 def train_state_dict(net, lr_schedule: bool = True) -> Dict:
-    """The device network's parameters + Adam state as a flax TrainState state dict."""
-    import torch  # noqa: F401  (net tensors live on the device)
-
-    from ..learners import params as P
+    """The device network's parameters + Adam state as a flax TrainState state dict, over the network's own
+    parameter tree (``net.spec``, learners/params.py): the same for every network."""
 
     def tree_of(buf):
-        flat = P.to_flax(buf.detach().cpu().numpy(), net.H, net.L, net.A, net.M, net.mode, net.E)
-        return nest({k: v.astype(np.float32) for k, v in flat.items()})
+        return nest({k: v.astype(np.float32) for k, v in net.spec.to_flax(buf.detach().cpu().numpy()).items()})
 
     count = np.asarray(net.adam_count, dtype=np.int32)
     return {
@@ -108,45 +105,8 @@ def load_train_state(net, state: Dict, reset_optimizer: bool = False) -> None:
     """Restore params (and, unless reset_optimizer, the Adam moments / count) into the device net."""
     import torch
 
-    from ..learners import params as P
-
     def buf_of(tree):
-        return torch.from_numpy(P.from_flax(flatten(tree), net.H, net.L, net.A, net.M, net.mode, net.E))
-
-    net.params.copy_(buf_of(state["params"]))
-    if reset_optimizer:
-        net.adam_m.zero_()
-        net.adam_v.zero_()
-        net.adam_count = 0
-        return
-    adam = state["opt_state"]["0"]
-    net.adam_m.copy_(buf_of(adam["mu"]))
-    net.adam_v.copy_(buf_of(adam["nu"]))
-    net.adam_count = int(np.asarray(adam["count"]))
-
-
-def single_train_state_dict(net, lr_schedule: bool = True) -> Dict:
-    """train_state_dict for the single-agent network (learners/single_gnn.py, params.single_layout): the same
-    TrainState state dict over that network's own parameter tree (its layout hooks)."""
-
-    def tree_of(buf):
-        return nest({k: v.astype(np.float32) for k, v in net._to_flax(buf.detach().cpu().numpy()).items()})
-
-    count = np.asarray(net.adam_count, dtype=np.int32)
-    return {
-        "step": np.asarray(net.adam_count, dtype=np.int32),
-        "params": tree_of(net.params),
-        "opt_state": {"0": {"count": count, "mu": tree_of(net.adam_m), "nu": tree_of(net.adam_v)},
-                      "1": {"count": count} if lr_schedule else {}},
-    }
-
-
-def load_single_train_state(net, state: Dict, reset_optimizer: bool = False) -> None:
-    """load_train_state for the single-agent network."""
-    import torch
-
-    def buf_of(tree):
-        return torch.from_numpy(net._from_flax(flatten(tree)))
+        return torch.from_numpy(net.spec.from_flax(flatten(tree)))
 
     net.params.copy_(buf_of(state["params"]))
     if reset_optimizer:

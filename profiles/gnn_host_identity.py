@@ -192,10 +192,12 @@ def run(tree, dry):
     return {"dry": dry, "call_table": rec.calls, "configs": configs}
 
 
-def compare(pa, pb):
+def compare(pa, pb, keys=("flops", "labels", "sha256", "calls"), tool="gnn_host_identity",
+            what="traces, output hashes, flops and label tables"):
+    """``keys``: what is compared per configuration besides the trace (learner_host_identity.py passes its own)."""
     a, b = (json.load(open(p)) for p in (pa, pb))
     if a["dry"] != b["dry"]:
-        sys.exit("gnn_host_identity: one file is a --dry run, the other is not")
+        sys.exit(f"{tool}: one file is a --dry run, the other is not")
     bad = 0
     for name in sorted(set(a["configs"]) | set(b["configs"]), key=lambda n: list(a["configs"]).index(n)
                        if n in a["configs"] else 1 << 30):
@@ -210,7 +212,7 @@ def compare(pa, pb):
             i = next((i for i, (x, y) in enumerate(zip(ta, tb)) if x != y), min(len(ta), len(tb)))
             diffs.append(f"call {i} of {len(ta)} / {len(tb)}:\n    {ta[i] if i < len(ta) else '(end)'}\n    "
                          f"{tb[i] if i < len(tb) else '(end)'}")
-        for key in ("flops", "labels", "sha256", "calls"):
+        for key in keys:
             if ca.get(key) != cb.get(key):
                 diffs.append(f"{key}: {ca.get(key)} != {cb.get(key)}")
         if diffs:
@@ -218,14 +220,15 @@ def compare(pa, pb):
             print(f"{name}: DIFFERS\n  " + "\n  ".join(diffs))
     n = len(a["configs"])
     calls = sum(c["calls"] for c in a["configs"].values())
-    what = "traces, flops and label tables" if a["dry"] else "traces, output hashes, flops and label tables"
-    print(f"gnn_host_identity: {pa} vs {pb}: {n} configurations, {calls} calls; {what}: "
+    what = "traces, flops and label tables" if a["dry"] else what
+    print(f"{tool}: {pa} vs {pb}: {n} configurations, {calls} calls; {what}: "
           f"{'identical' if not bad else f'{bad} configurations differ'}")
     sys.exit(1 if bad else 0)
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+def main(run=run, compare=compare, doc=__doc__, name="gnn_host_identity"):
+    """--tree / --out / --dry / --compare over ``run(tree, dry)`` and ``compare(json, json)``."""
+    ap = argparse.ArgumentParser(description=doc, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--tree", default=HERE, help="root of the source tree to run (default: this file's)")
     ap.add_argument("--out", default=None, help="JSON to write")
     ap.add_argument("--dry", action="store_true", help="no GPU: record the calls without making them")
@@ -240,7 +243,7 @@ def main():
     with open(args.out, "w") as f:
         json.dump(res, f, separators=(",", ":"))
         f.write("\n")
-    print(f"gnn_host_identity: {len(res['configs'])} configurations, "
+    print(f"{name}: {len(res['configs'])} configurations, "
           f"{sum(c['calls'] for c in res['configs'].values())} calls -> {args.out}")
 
 

@@ -51,7 +51,7 @@ def _run_and_check(shape, MB, sizes, micro, tag, pool=None, micro_samples=None):
         seen.append((b.g0, b.G, b.S))
         return b
 
-    import marlsat.learners.bc_learner as bcl
+    import marlsat.learners.base as bcl  # the learners' one assemble call (Learner._batch)
 
     learner.trace = []
     p0 = net.to_flax()

@@ -136,11 +136,12 @@ def test_every_adam_step_of_an_epoch_matches_oracle(precision_path):
 def test_micro_batches_meet_the_same_bars():
     """An activation budget of one sample: minibatches of 2 run as two micro-batches."""
     from marlsat.learners import gnn
+    from marlsat.learners.base import activation_bytes_per_sample
 
     prev = gnn.set_precision("fp16x2")
     try:
         rows = V + C
-        budget = 1.5 * (4.0 * L * rows * 12 * H + 4.0 * rows * 24 * H)  # mappo_gnn_sat_learner.activation_plan
+        budget = 1.5 * activation_bytes_per_sample(rows, H, L)
         learner, net, env, data = _learner(micro_bytes=budget)
         assert learner.micro == 1
         learner.trace = []

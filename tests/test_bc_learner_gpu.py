@@ -251,7 +251,9 @@ def test_micro_batches_meet_the_same_bars():
     probe, _, _ = _learner(V, C, vpa, H, L, MB=4, n=7)
     assert probe.micro == 4
     rows = probe.tpl.mean_full_rows
-    budget = 2.5 * (4.0 * L * rows * 12 * H + 4.0 * rows * 24 * H)  # learners.mappo_gnn_sat_learner.activation_plan
+    from marlsat.learners.base import activation_bytes_per_sample
+
+    budget = 2.5 * activation_bytes_per_sample(rows, H, L)
     learner, net, env = _learner(V, C, vpa, H, L, MB=4, n=7, micro_bytes=budget)
     assert learner.micro == 2
     learner.trace = []

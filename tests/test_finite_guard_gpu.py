@@ -32,7 +32,7 @@ def _learner(clauses, V, C, vpa, cfg):
 
 
 def test_isolated_variable_at_depth16_raises():
-    from marlsat.learners.mappo_gnn_sat_learner import NO_BAD_STEP
+    from marlsat.learners.base import NO_BAD_STEP
     from marlsat.random import PRNGKey
     from marlsat.utils.generate_cnf_dataset import generate_sat_clauses, has_isolated_variable
 
@@ -51,7 +51,7 @@ def test_isolated_variable_at_depth16_raises():
 
 
 def test_clean_pool_passes_the_guard():
-    from marlsat.learners.mappo_gnn_sat_learner import NO_BAD_STEP
+    from marlsat.learners.base import NO_BAD_STEP
     from marlsat.random import PRNGKey
     from marlsat.utils.generate_cnf_dataset import generate_problem_pool
 

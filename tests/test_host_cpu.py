@@ -97,6 +97,56 @@ def test_flax_tree_nesting_matches_param_layout():
     np.testing.assert_array_equal(back, P.init_flat(64, 2, 3, 4, 0, seed=1))
 
 
+# sha256 of init_flat's fp32 bytes at (H, L, seed), recorded from the commit before params.Spec (three codecs, one per
+# network): the spec-driven codec must draw from the generator in the same order
+INIT_SHA256 = {
+    "mappo": {(64, 2, 0): "eac2ae2eee07ec63e6f9c3c83649c2965a8bfd0279a9bd052d09adb160abf7bf",
+              (64, 2, 3): "1dab246e1e157cd0cdebd2b2fa7889a135e8c2200c45e3e6f5e26dc73923bb5c",
+              (128, 3, 0): "76f5e56fde4ccd3b9194c7cdc3e1895ae9d08917615c11d08cac91151cf9a1e3",
+              (128, 3, 3): "51626d6d52a6a5a4201d99b0a34052d0505962b760b83be19be9b526545d3838"},
+    "mappo_mode1": {(64, 2, 0): "ef3777248e1bf748ab968cfc7358a034b7a1880963a2003f1ad7c0640a784d5c",
+                    (64, 2, 3): "bd05c3f563d5061a51501311e814ffb95dca3681f22aa8619ae6baf9825fe467",
+                    (128, 3, 0): "1b4db5c83bb3ec3c06ef94f10f83a349af7602292faa4a03addde6f7857ec943",
+                    (128, 3, 3): "0042b78f909460f5ab96b93bb9146d56d17352c591ed16a28501e89b983d6559"},
+    "single": {(64, 2, 0): "d52e7f42125331d23234fc8d352a32fc8d91ba76502d5038f21a542b2dfd5e01",
+               (64, 2, 3): "82b73867ce9140269c93c84beb72dd1acb7ee8d6ee8565597d874802bdfb9716",
+               (128, 3, 0): "6c70287c9cd0ee8ae83c93c2c0ba8dfee557f7e7b41826382b0560f5d476ae51",
+               (128, 3, 3): "68290fa2a75229aee430371ee047d7c31728d73cc39c6a6a372da878e4671d16"},
+    "assign": {(64, 2, 0): "7430c8510e84e6d4bba26819b3bcfbf6b52a00b3fd766edb30424bb412b76472",
+               (64, 2, 3): "ee715990ffdeec6318afc1b9d38914f1fbc59598f98b7d29464739427cbc5935",
+               (128, 3, 0): "5f98f52309b52f73a54c4866a8e386b718920a5651f0b35fb61e60845af13f41",
+               (128, 3, 3): "383eb8a165b47618da0c7809092a0a385bf9adc80bb8eca4f8590e3acb2664ea"},
+}
+
+
+@pytest.mark.parametrize("network", sorted(INIT_SHA256))
+def test_param_codec_init_hashes_and_roundtrip(network):
+    """The three networks' trees through the one codec (params.Spec): init_flat is bitwise what the per-network
+    codecs drew, the public one-line wrappers agree with the spec, and a flat buffer survives to_flax -> from_flax
+    bitwise.  The buffer is the image of a random tree: the layout's alignment padding and the two zero blocks of a
+    GRU's hidden bias [0 | 0 | b_hn] are not in the tree, so an arbitrary buffer could not come back."""
+    import hashlib
+
+    from marlsat.learners import params as P
+
+    for (H, L, seed), want in INIT_SHA256[network].items():
+        spec, init = {"mappo": (P.spec(H, L, 2, 10, 0, 16), lambda: P.init_flat(H, L, 2, 10, 0, 16, seed)),
+                      "mappo_mode1": (P.spec(H, L, 4, 4, 1, 16), lambda: P.init_flat(H, L, 4, 4, 1, 16, seed)),
+                      "single": (P.single_spec(H, L), lambda: P.single_init_flat(H, L, seed)),
+                      "assign": (P.assign_spec(H, L), lambda: P.assign_init_flat(H, L, seed))}[network]
+        flat = init()
+        assert flat.dtype == np.float32
+        assert hashlib.sha256(flat.tobytes()).hexdigest() == want, (network, H, L, seed)
+        assert np.array_equal(spec.init_flat(seed).view(np.int32), flat.view(np.int32))
+        rng = np.random.default_rng(seed + 11)
+        tree = {k: rng.standard_normal(shp).astype(np.float32) for k, shp in spec.shapes.items()}
+        x = spec.from_flax(tree)
+        back = spec.to_flax(x)
+        assert set(back) == set(tree) and all(np.array_equal(back[k].view(np.int32), tree[k].view(np.int32))
+                                              for k in tree)
+        assert np.array_equal(spec.from_flax(back).view(np.int32), x.view(np.int32))
+
+
 def test_config_overrides_and_solution_line(tmp_path):
     from marlsat.runners.mappo_runner import flat_config, load_config, solution_line
 

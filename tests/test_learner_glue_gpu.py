@@ -1,8 +1,6 @@
 """GPU: the learner glue kernels (learner_kernels.hip) -- the epoch permutation, the micro-batch row
 gather and the cycle metrics -- against numpy on the same inputs (bit-exact for indices and copies,
 fp64 sums to 1e-12 relative)."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -44,7 +42,9 @@ def test_permutation_mixes_uniformly():
 
 
 def test_gather_rows_matches_indexing():
-    from marlsat import _lib
+    """The learners' row gather (learners/base.gather_rows): rollout buffers with two leading dimensions (T, B, ...)
+    and the same tensors as a dataset with one, (T*B, ...)."""
+    from marlsat.learners.base import gather_rows
 
     g = torch.Generator(device="cuda").manual_seed(0)
     T, B, V, A = 4, 50, 37, 5
@@ -53,14 +53,11 @@ def test_gather_rows_matches_indexing():
             torch.randint(0, 9, (T, B, A), dtype=torch.int32, device="cuda", generator=g),
             torch.randn(T, B, A, device="cuda", generator=g), torch.randn(T, B, device="cuda", generator=g)]
     idx = torch.randint(0, T * B, (77,), dtype=torch.int32, device="cuda", generator=g)
-    outs = [torch.empty((77,) + tuple(t.shape[2:]), dtype=t.dtype, device="cuda") for t in srcs]
-    n = len(srcs)
-    src = (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs])
-    dst = (ctypes.c_void_p * n)(*[t.data_ptr() for t in outs])
-    rb = (ctypes.c_int32 * n)(*[t[0, 0].numel() * t.element_size() for t in srcs])
-    _lib.check(_lib.lib.msat_gather_rows(idx.data_ptr(), 77, n, src, dst, rb, _lib.stream_ptr()), "gather")
-    for t, o in zip(srcs, outs):
-        assert torch.equal(o, t.reshape((T * B,) + tuple(t.shape[2:]))[idx.long()])
+    flat = [t.reshape((T * B,) + tuple(t.shape[2:])) for t in srcs]
+    for outs in (gather_rows(idx, srcs, lead=2), gather_rows(idx, flat, lead=1)):
+        assert len(outs) == len(srcs)
+        for t, o in zip(flat, outs):
+            assert o.dtype == t.dtype and torch.equal(o, t[idx.long()])
 
 
 def test_cycle_metrics_match_numpy():

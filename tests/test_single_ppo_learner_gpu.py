@@ -294,6 +294,7 @@ def test_every_adam_step_of_a_cycle_matches_oracle(shape_no, precision_path, max
 def test_micro_batches_meet_the_same_bars():
     """An activation budget of 2 samples: minibatches of 6 run as micro-batches of 2 + 2 + 2."""
     from marlsat.learners import gnn
+    from marlsat.learners.base import activation_bytes_per_sample
     from marlsat.random import PRNGKey
 
     prev = gnn.set_precision("fp16x2")
@@ -304,7 +305,7 @@ def test_micro_batches_meet_the_same_bars():
         probe, _, _ = _learner(V, C, H, L, cfg, max_steps=6)
         rows = probe.tpl.mean_full_rows - probe.tpl.mean_actor_rows
         assert rows == V + C
-        budget = 2.5 * (4.0 * L * rows * 12 * H + 4.0 * rows * 24 * H)  # mappo_gnn_sat_learner.activation_plan
+        budget = 2.5 * activation_bytes_per_sample(rows, H, L)
         learner, net, pool = _learner(V, C, H, L, cfg, max_steps=6, micro_bytes=budget)
         assert learner.micro == 2
         learner.trace = []
