@@ -1,6 +1,7 @@
 """Host replay of msat_dpll (include/marlsat.h): a plain NumPy/Python restatement of the header's algorithm on the
 int32 clause array, one sample at a time, written for clarity.  The yardstick of tests/test_dpll_*.py.  It shares no
-code with the library.
+code with the library.  A pass judges all clauses in one NumPy expression (every clause against the assignment of the
+pass's start, as the header has it); the search around it is plain Python.
 
 A literal l > 0 is the code 2 (l - 1), true iff x[l - 1] == 1; l < 0 is the code 2 (-l - 1) + 1, true iff
 x[-l - 1] == 0; l == 0 is the null literal: always false, no real slot.
@@ -11,91 +12,97 @@ UNKNOWN, SAT, UNSAT = 0, 1, 2
 UNSET = -1
 
 
-def _judge(clause_codes, x):
-    """One clause against x: (has a true slot, the codes of its unassigned real slots in slot order)."""
-    true, free = False, []
-    for c in clause_codes:
-        v = c >> 1
-        if x[v] == UNSET:
-            free.append(c)
-        elif (x[v] ^ c) & 1:
-            true = True
-    return true, free
+def _judge(code, real, x):
+    """Every clause against x (V,) int8: (open (C,) bool: the clause has no true slot, free (C, K) bool: its
+    unassigned real slots)."""
+    val = x[code >> 1]
+    free = real & (val == UNSET)
+    true = real & (val != UNSET) & (((val ^ code) & 1) == 1)
+    return ~true.any(axis=1), free
 
 
-def replay_one(clauses, num_vars, cube=0, cube_bits=0, max_nodes=0):
-    """One sample: (status, x (V,) uint8, nodes, conflicts, propagations)."""
+def replay_one(clauses, num_vars, cube=0, cube_bits=0, max_nodes=0, stats=None):
+    """One sample: (status, x (V,) uint8, nodes, conflicts, propagations).  A dict passed as `stats` receives what
+    the search went through: "max_level" (the largest L reached), "deepest_flip" (the deepest level at which an entry
+    was flipped, 0 if none), "max_pops" (the most closed entries popped by one conflict) and "flips" (per flip, in
+    order: (L when the conflict arose, the level flipped)).  The outputs do not depend on it."""
+    if stats is not None:
+        stats.update(max_level=0, deepest_flip=0, max_pops=0, flips=[])
     V = int(num_vars)
-    # real slots only: the codes of every clause, in slot order
-    codes = [[(abs(int(l)) - 1) * 2 + (1 if l < 0 else 0) for l in cl if l != 0] for cl in np.asarray(clauses)]
-    x = [UNSET] * V
-    level = [0] * V
+    lits = np.asarray(clauses, dtype=np.int64)
+    real = lits != 0  # the real slots; a null slot's code is never looked at
+    code = np.where(real, (np.abs(lits) - 1) * 2 + (lits < 0), 0)
+    rows = np.arange(code.shape[0])
+    x = np.full(V, UNSET, dtype=np.int8)
+    level = np.zeros(V, dtype=np.int64)
     stack = []  # entry L-1: [variable, phase, closed]
     nodes = conflicts = props = 0
 
     def result(status):
         out = np.zeros(V, dtype=np.uint8)
         if status == SAT:
-            out[:] = [1 if b == 1 else 0 for b in x]
+            out[:] = x == 1
         return status, out, nodes, conflicts, props
 
     while True:
         # step 1: synchronous passes
         conflict = False
         for _ in range(V + 1):
-            judged = [_judge(c, x) for c in codes]  # against the assignment at the start of the pass
-            if any(not t and not free for t, free in judged):
+            open_, free = _judge(code, real, x)  # against the assignment at the start of the pass
+            k = free.sum(axis=1)
+            if (open_ & (k == 0)).any():
                 conflict = True
                 break
-            units = sorted({free[0] for t, free in judged if not t and free and all(f == free[0] for f in free)})
-            if not units:
+            first = code[rows, free.argmax(axis=1)]  # the code of the first unassigned real slot
+            same = ((code == first[:, None]) | ~free).all(axis=1)
+            units = np.unique(first[open_ & (k > 0) & same])
+            if units.size == 0:
                 break
-            unit_vars = {c >> 1 for c in units}
+            unit_vars = np.unique(units >> 1)
             if len(unit_vars) < len(units):  # some variable has both signs
                 conflict = True
                 break
-            for c in units:
-                x[c >> 1] = 1 - (c & 1)  # the code becomes true
-                level[c >> 1] = len(stack)
+            x[units >> 1] = 1 - (units & 1)  # the code becomes true
+            level[units >> 1] = len(stack)
             props += len(unit_vars)
         else:
             raise AssertionError("more than V + 1 passes")
 
         if conflict:  # step 2
             conflicts += 1
+            before = len(stack)
             while stack and stack[-1][2]:
                 stack.pop()
             L = len(stack)
+            if stats is not None:
+                stats["max_pops"] = max(stats["max_pops"], before - L)
             if L == 0:
                 return result(UNSAT)
-            for v in range(V):
-                if x[v] != UNSET and level[v] >= L:
-                    x[v] = UNSET
+            x[(x != UNSET) & (level >= L)] = UNSET
             if nodes == max_nodes:
                 return result(UNKNOWN)
             nodes += 1
+            if stats is not None:
+                stats["deepest_flip"] = max(stats["deepest_flip"], L)
+                stats["flips"].append((before, L))
             v, phase, _ = stack[-1]
             stack[-1] = [v, phase ^ 1, True]
             x[v], level[v] = phase ^ 1, L
             continue
 
-        judged = [_judge(c, x) for c in codes]
-        opens = [free for t, free in judged if not t]
-        if not opens:  # step 3
+        open_, free = _judge(code, real, x)
+        if not open_.any():  # step 3
             return result(SAT)
 
         if nodes == max_nodes:  # step 4
             return result(UNKNOWN)
-        cnt = [0] * (2 * V)
-        for free in opens:
-            w = 4 if len(free) == 2 else 1
-            for c in free:
-                cnt[c] += w
-        best, v = -1, -1
-        for u in range(V):
-            if x[u] == UNSET and cnt[2 * u] + cnt[2 * u + 1] > best:
-                best, v = cnt[2 * u] + cnt[2 * u + 1], u
-        assert best > 0
+        counted = free & open_[:, None]  # the unassigned real slots of the open clauses, duplicates included
+        weight = np.where(free.sum(axis=1) == 2, 4, 1)
+        cnt = np.zeros(2 * V, dtype=np.int64)
+        np.add.at(cnt, code[counted], np.broadcast_to(weight[:, None], code.shape)[counted])
+        score = np.where(x == UNSET, cnt[0::2] + cnt[1::2], -1)
+        v = int(score.argmax())  # the lowest index on ties
+        assert score[v] > 0
         phase = 1 if cnt[2 * v] >= cnt[2 * v + 1] else 0
         L = len(stack) + 1
         nodes += 1
@@ -104,6 +111,8 @@ def replay_one(clauses, num_vars, cube=0, cube_bits=0, max_nodes=0):
             phase = (int(cube) >> (L - 1)) & 1
         stack.append([v, phase, closed])
         x[v], level[v] = phase, L
+        if stats is not None:
+            stats["max_level"] = max(stats["max_level"], L)
 
 
 def replay(clauses, num_vars, problem_idx, cubes=None, cube_bits=0, max_nodes=0):

@@ -147,7 +147,9 @@ def test_planted_pools(V, C, sid):
 
 
 def test_past_256_variables():
-    """V = 300, C = 1290: 16-bit levels and byte indices past 255, 21 clause passes."""
+    """V = 300, C = 1290: variable numbers and value-byte indices past 255, 21 clause passes.  These planted searches
+    end at level 143 and 144 without a conflict; levels past 255, the reason the level array is 16 bits wide, are
+    reached by the chain instances of tests/test_dpll_edges_gpu.py."""
     from marlsat.utils.generate_cnf_dataset import generate_sat_clauses
 
     pool = np.stack([generate_sat_clauses(300, 1290, 3, 700 + i) for i in range(2)])
