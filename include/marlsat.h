@@ -260,6 +260,12 @@ int msat_env_group_launch_threads(int32_t total_envs);
  * delta write is the default of, chosen for that kernel; for every other desc msat_env_launch_threads' value.
  * MARLSAT_ENV_THREADS forces both.  (Additive as well: msat_version() stays 3.) */
 int msat_env_delta_launch_threads(const msat_env_desc *desc);
+/* 1 if an msat_env_step_delta launch of desc with an obs shadow takes a step kernel compiled for desc's own
+ * geometry (num_vars, num_clauses, num_agents; clause_width 3) instead of the kernel of any shape, else 0 (a bad
+ * desc included).  Such a kernel exists for uf200-860 with 25 agents, int32 observations, at the delta rule's 256
+ * lanes; it computes what the kernel of any shape computes.  MARLSAT_ENV_STATIC=0 (read once per process) turns
+ * every such kernel off.  Host-only: no GPU call.  (Additive as well: msat_version() stays 3.) */
+int msat_env_static_shape(const msat_env_desc *desc);
 
 /* obs may be NULL in msat_env_reset / msat_env_step: state-only update, no observation write
  * (the single-agent SatEnv observes the GNN input instead, src/envs/sat_env.py:120-166). */

@@ -1169,6 +1169,33 @@ env_kernel(EnvParams p, msat_pool pool, msat_env_state st, const int32_t *__rest
                                  cs, sa);
     cs.finish();
 }
+
+// The same kernel compiled for one geometry: an overload with the Shape (a StaticShape, env_params.h) as a fourth
+// template argument, the same arguments and the same body behind pin_shape, which gives p's geometry fields the
+// shape's constants.  The host's only choice is which of the two to launch (launch_env_kernel).  An overload and a
+// body of its own, not a defaulted parameter or a shared body: either changes the symbols or the code of the
+// kernels above (profiles/kernel_identity.py), which every other shape keeps running.
+template <int MODE, typename ObsT, int T, class Shape>
+__global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T >= MSAT_SHADOW_W8_MIN_T ? 8 : 1, 8)))
+env_kernel(EnvParams p, msat_pool pool, msat_env_state st, const int32_t *__restrict__ actions,
+           const uint8_t *__restrict__ reset_mask, const int32_t *__restrict__ new_pidx,
+           const uint8_t *__restrict__ new_assign, uint64_t seed, uint64_t ctr, msat_step_out out,
+           ObsT *__restrict__ obs, uint32_t *__restrict__ shadow_rows, int shadow_g) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    pin_shape<Shape>(p);
+    const ObsShadowArg sa{shadow_rows, shadow_g};
+    const int side = (MODE == kModeStepAutoReset && p.rq_mode == 1) ? p.rq_cap : 0;
+    if ((int)blockIdx.x < side) {
+        env_side_reset<ObsT, T, true>(p, pool, st, new_pidx, new_assign, seed, ctr, obs, (int)blockIdx.x, smem,
+                                      sa);
+        return;
+    }
+    const int b = xcd_major((int)blockIdx.x - side, p.B, p.ablate & 4);
+    const ClockStamp cs(out.clock_stamps, b);
+    env_run<MODE, ObsT, T, true>(p, pool, st, actions, reset_mask, new_pidx, new_assign, seed, ctr, out, obs, b, smem,
+                                 cs, sa);
+    cs.finish();
+}
 }  // namespace shadow
 
 // Ragged batches (BASELINE config 5): several size classes, each its own (V, C, A) batch with its own
@@ -1297,8 +1324,31 @@ static void for_width_dtype(int T, int obs_dtype, F f) {
         f(int8_t{}, std::integral_constant<int, T0>{});
 }
 
+// The shapes shadow::env_kernel is also compiled for (int32 observations, the delta rule's 256 lanes): uf200-860 with
+// 25 agents, the bench's headline shape.  MSAT_STATIC_ALL_WIDTHS: A/B builds only (make ab), the same at every width.
+using StaticUf200 = StaticShape<200, 860, 25>;
+#ifndef MSAT_STATIC_ALL_WIDTHS
+#define MSAT_STATIC_ALL_WIDTHS 0
+#endif
+
+// MARLSAT_ENV_STATIC=0, read once per process: every launch takes the kernel of any shape
+static bool env_static_enabled() {
+    static const bool on = [] {
+        const char *e = getenv("MARLSAT_ENV_STATIC");
+        return !(e && e[0] == '0' && e[1] == '\0');
+    }();
+    return on;
+}
+
+// Whether a launch with an obs shadow, these parameters, this obs dtype and T lanes takes StaticUf200's kernel: the
+// run-time geometry equals the shape's constants field by field
+static bool takes_static_shape(const EnvParams &p, int obs_dtype, int T) {
+    return env_static_enabled() && obs_dtype == MSAT_OBS_I32 && (T == 256 || MSAT_STATIC_ALL_WIDTHS) &&
+           shape_matches<StaticUf200>(p);
+}
+
 // One (MODE, ObsT, T) launch: shadow::env_kernel for a step with an obs shadow (modes 1 and 2 alone have that
-// kernel), env_kernel otherwise
+// kernel; the one of StaticUf200 where takes_static_shape), env_kernel otherwise
 template <int MODE, typename ObsT, int T>
 static void launch_env_kernel(int grid, size_t lds, hipStream_t s, const EnvParams &p, const msat_pool &pool,
                               const msat_env_state &st, const int32_t *actions, const uint8_t *mask,
@@ -1306,6 +1356,14 @@ static void launch_env_kernel(int grid, size_t lds, hipStream_t s, const EnvPara
                               const msat_step_out &o, void *obs, const ObsShadowArg &sa) {
     if constexpr (MODE == kModeStep || MODE == kModeStepAutoReset) {
         if (sa.rows != nullptr) {
+            if constexpr (std::is_same<ObsT, int32_t>::value && (T == 256 || MSAT_STATIC_ALL_WIDTHS)) {
+                if (takes_static_shape(p, MSAT_OBS_I32, T)) {
+                    hipLaunchKernelGGL((shadow::env_kernel<MODE, ObsT, T, StaticUf200>), dim3(grid), dim3(T), lds, s,
+                                       p, pool, st, actions, mask, npidx, nassign, seed, ctr, o, (ObsT *)obs, sa.rows,
+                                       sa.g);
+                    return;
+                }
+            }
             hipLaunchKernelGGL((shadow::env_kernel<MODE, ObsT, T>), dim3(grid), dim3(T), lds, s, p, pool, st, actions,
                                mask, npidx, nassign, seed, ctr, o, (ObsT *)obs, sa.rows, sa.g);
             return;
@@ -1448,6 +1506,12 @@ extern "C" int msat_env_delta_launch_threads(const msat_env_desc *desc) {
     EnvParams p;
     if (int rc = make_params(desc, &p)) return rc;
     return env_delta_threads(p, desc->obs_dtype);
+}
+
+extern "C" int msat_env_static_shape(const msat_env_desc *desc) {
+    EnvParams p;
+    if (make_params(desc, &p)) return 0;
+    return takes_static_shape(p, desc->obs_dtype, env_delta_threads(p, desc->obs_dtype)) ? 1 : 0;
 }
 
 extern "C" int msat_env_group_launch_threads(int32_t total_envs) {

@@ -5,6 +5,8 @@
 #pragma once
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace msat {
@@ -26,6 +28,47 @@ struct EnvParams {
     int rq_mode, rq_cap;
     uint32_t rq_serial;
 };
+
+// What follows from (V, C, A) alone: the one place make_params and StaticShape derive it.
+struct EnvGeom {
+    int base, rem, M, D, WV, WC;
+};
+
+__host__ __device__ constexpr EnvGeom env_geom(int V, int C, int A) {
+    return EnvGeom{V / A, V % A, V / A + (V % A > 0 ? 1 : 0), 2 * V + C, 2 * ((V + 63) / 64), 2 * ((C + 63) / 64)};
+}
+
+// The Shape parameter of shadow::env_kernel (env_kernels.hip).  DynShape: every geometry field is the run-time
+// argument it always was.  StaticShape<V, C, A>: a kernel compiled for that one geometry (3-literal clauses) --
+// pin_shape overwrites the fields at kernel entry, every helper is inlined, and the divisions, clamps, tail loops
+// and argument registers that served other shapes fold away.  The host takes such a kernel only for a launch whose
+// EnvParams equal the constants field by field (shape_matches).
+struct DynShape {};
+
+template <int V_, int C_, int A_>
+struct StaticShape {
+    static_assert(V_ >= 1 && C_ >= 1 && A_ >= 1 && A_ <= V_, "StaticShape: not a geometry make_params accepts");
+    static constexpr int V = V_, C = C_, A = A_, K = 3;
+    static constexpr int base = env_geom(V_, C_, A_).base, rem = env_geom(V_, C_, A_).rem;
+    static constexpr int M = env_geom(V_, C_, A_).M, D = env_geom(V_, C_, A_).D;
+    static constexpr int WV = env_geom(V_, C_, A_).WV, WC = env_geom(V_, C_, A_).WC;
+};
+
+template <class Shape>
+__device__ __forceinline__ void pin_shape(EnvParams &p) {
+    if constexpr (!std::is_same<Shape, DynShape>::value) {
+        p.V = Shape::V, p.C = Shape::C, p.A = Shape::A, p.K = Shape::K;
+        p.base = Shape::base, p.rem = Shape::rem, p.M = Shape::M, p.D = Shape::D;
+        p.WV = Shape::WV, p.WC = Shape::WC;
+    }
+}
+
+template <class Shape>
+inline bool shape_matches(const EnvParams &p) {
+    return p.V == Shape::V && p.C == Shape::C && p.A == Shape::A && p.K == Shape::K && p.base == Shape::base &&
+           p.rem == Shape::rem && p.M == Shape::M && p.D == Shape::D && p.WV == Shape::WV &&
+           p.WC == Shape::WC;
+}
 
 __host__ __device__ __forceinline__ int agent_lo(const EnvParams &p, int i) { return i * p.base + (i < p.rem ? i : p.rem); }
 __host__ __device__ __forceinline__ int agent_size(const EnvParams &p, int i) { return p.base + (i < p.rem ? 1 : 0); }
@@ -54,14 +97,15 @@ inline int make_params(const msat_env_desc *d, EnvParams *p) {
     p->C = d->num_clauses;
     p->K = d->clause_width;
     p->A = d->num_agents;
-    p->base = p->V / p->A;
-    p->rem = p->V % p->A;
-    p->M = p->base + (p->rem > 0 ? 1 : 0);
+    const EnvGeom g = env_geom(p->V, p->C, p->A);
+    p->base = g.base;
+    p->rem = g.rem;
+    p->M = g.M;
     MSAT_REQUIRE(d->max_vars_per_agent == p->M, "max_vars_per_agent %d != ceil(V/A)=%d",
                  d->max_vars_per_agent, p->M);
-    p->WV = 2 * ((p->V + 63) / 64);
-    p->WC = 2 * ((p->C + 63) / 64);
-    p->D = 2 * p->V + p->C;
+    p->WV = g.WV;
+    p->WC = g.WC;
+    p->D = g.D;
     p->max_steps = d->max_steps;
     p->action_mode = d->action_mode;
     p->reward_mode = d->reward_mode;

@@ -137,6 +137,7 @@ def _load():
         "msat_reset_queue_words": (c_size_t, [c_int32]),
         "msat_env_launch_threads": (c_int32, [POINTER(EnvDesc)]),
         "msat_env_delta_launch_threads": (c_int32, [POINTER(EnvDesc)]),
+        "msat_env_static_shape": (c_int32, [POINTER(EnvDesc)]),
         "msat_env_group_launch_threads": (c_int32, [c_int32]),
         "msat_gae_workspace_bytes": (c_size_t, [c_int32, c_int32]),
         "msat_gae": (
@@ -370,6 +371,7 @@ EXPORTED = (
     "msat_reset_queue_words",
     "msat_env_launch_threads",
     "msat_env_delta_launch_threads",
+    "msat_env_static_shape",
     "msat_env_group_launch_threads",
 )
 
